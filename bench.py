@@ -6,9 +6,11 @@ SP.trainSP's loop (reference SP.py:132-138): model_SP forward (train-mode BN) ->
 zero_grad, every kernel hand-written HIP behind the C-ABI.  Inputs are resident in HBM before the timed region.
 N>1: one process per GPU (torch.distributed.run), gradient all-reduce over RCCL overlapped with backward.
 
-Prints ONE JSON line on rank 0 (contract in the task prompt) with `roofline` (dominant kernel: the f32-MFMA
-implicit-GEMM 3x3 conv, timed live with HIP events on the launch stream) and `cpu_baseline` (the oracle, i.e.
-the reference's PyTorch-CPU algorithm, timed on this box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets up,
+warms up, times exactly --steps steps and prints the line.  --full adds every other measurement: `roofline` (dominant
+kernel: the f32-MFMA implicit-GEMM 3x3 conv, timed live with HIP events on the launch stream), `cpu_baseline` (the
+oracle, i.e. the reference's PyTorch-CPU algorithm, timed on this box's host cores on a bounded sample), the untimed
+legs under `extra` and the weak-scaling bookkeeping.  --dump-outputs DIR writes what the last timed step computed.
 """
 import argparse
 import json
@@ -122,14 +124,56 @@ def cpu_baseline(batch=8, size=224, threads=16, timed_steps=3):
                       f"(profiles/r06_cpu_baseline_b32.txt) -- batch 8 is the bounded sample, and the faster of the two per frame"}
 
 
+DUMP_CAP = 1 << 21          # elements per dumped array (8 MiB of float32): seven arrays stay below 64 MB at any --batch / --size
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_sample(t, seed):
+    """``t`` as float32 on the host, or, above DUMP_CAP elements, a fixed 1-D sample of DUMP_CAP of them: one element from
+    each of DUMP_CAP equal strides at a seeded offset, so the same size and seed always pick the same indices."""
+    t = t.detach().float()
+    n = t.numel()
+    if n > DUMP_CAP:
+        g = torch.Generator().manual_seed(seed)
+        pos = (torch.arange(DUMP_CAP, dtype=torch.float64) + torch.rand(DUMP_CAP, generator=g, dtype=torch.float64)) * (n / DUMP_CAP)
+        t = t.reshape(-1)[pos.long().clamp_(max=n - 1).to(t.device)]
+    return t.cpu().numpy()
+
+
+def dump_outputs(out_dir, kept, sp_opt, sp_model, at_opt):
+    """What a caller of the timed step receives from its last call: the losses and outputs of the SP and AT steps (snapshots
+    taken inside that step) and the parameters / BatchNorm running statistics the step left behind."""
+    import numpy as np
+    arrays = {"sp_loss": kept["sp_loss"].reshape(1), "sp_gaze_map": kept["sp_gaze_map"], "sp_params": sp_opt.flat_p,
+              "sp_bn_running_stats": torch.cat([b.reshape(-1) for b in sp_model.buffers() if b.is_floating_point()])}
+    if at_opt is not None:
+        arrays.update({"at_loss": kept["at_loss"].reshape(1), "at_output": kept["at_output"], "at_params": at_opt.flat_p})
+    arrays = {name: dump_sample(t, seed) for seed, (name, t) in enumerate(arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays, {total / 1e6:.1f} MB -> {out_dir}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=3,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region (--steps steps between barrier + synchronize) is run this many times back to back; "
-                         "value / ms_per_step are the MEDIAN region, extra.timed_repeats lists all of them")
+                         "value / ms_per_step are the MEDIAN region, extra.timed_repeats lists all of them (default: 1, "
+                         "with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: bare-MFMA probe, roofline / per-kernel profiled step, the untimed "
+                         "legs (AT alone, LF, opt-in backward arithmetic, exact f32, PCIe-inclusive, RCCL at world 1), the CPU "
+                         "baseline and the weak-scaling bookkeeping (each leg still honours its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "sp_loss, sp_gaze_map, sp_params, sp_bn_running_stats and, with the AT step, at_loss, at_output, "
+                         "at_params; an array above %d elements is a fixed, seeded sample of that many (rank 0 only)" % DUMP_CAP)
     ap.add_argument("--batch", type=int, default=32, help="frames per GPU (BASELINE: 32)")
     ap.add_argument("--size", type=int, default=224)
     ap.add_argument("--no-at", action="store_true", help="leave the AT (lstmnet T=16, B=32) training step out")
@@ -145,6 +189,7 @@ def main():
                     help="skip the opt-in two-product backward leg (extra.bwd2): every step of the run is then the default arithmetic "
                          "(what the committed kernel statistics / PMC profiles are collected with)")
     args = ap.parse_args()
+    repeats = max(1, args.repeats if args.repeats is not None else (3 if args.full else 1))
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU.
@@ -233,10 +278,12 @@ def main():
         c0 = torch.zeros(2, args.batch, 512, device=dev)
         opt_at.zero_grad()
 
-    def at_step():
+    def at_step(keep=None):
         # AT: forward + MSE + backward + Adam of the attention-transition LSTM (AT.py:138-145 at T=16, B=32)
         pred, _ = lstm(at_in, (h0, c0))
         l2 = MSELoss.apply(pred, at_tgt)
+        if keep is not None:                         # --dump-outputs: this step's results, copied on this step's stream
+            keep["at_output"], keep["at_loss"] = pred.detach().clone(), l2.detach().clone()
         l2.backward()
         opt_at.step()
         opt_at.zero_grad()
@@ -252,11 +299,14 @@ def main():
 
     prefetch_stream = streams.side_stream("input") if (streams.ENABLED and not args.no_input_prefetch) else None
 
-    def step(staged=None):
+    def step(staged=None, keep=None):
         # SP: the body of SP.trainSP's loop (SP.py:132-138); ``staged`` = (image, flow, gt) of this step when the batch
-        # crosses PCIe inside the step (the untimed PCIe-inclusive leg below), else the HBM-resident synthetic batch
+        # crosses PCIe inside the step (the untimed PCIe-inclusive leg below), else the HBM-resident synthetic batch;
+        # ``keep``: a dict that receives copies of this step's outputs (--dump-outputs, last timed step only)
         x_s, x_t, tgt = staged if staged is not None else (input_s, input_t, target)
         output = model(x_s, x_t)
+        if keep is not None:
+            keep["sp_gaze_map"] = output.detach().clone()
         if prefetch_stream is not None and staged is None and streams.ENABLED:
             # the NEXT step's input-side work (flow stack -> NHWC-32 + its abs-max: no weights involved), issued now on a helper
             # stream exactly as SP.trainSP's loader does for batch k + 1 (data.STdatas.staged_batches): it runs under this step's
@@ -264,6 +314,8 @@ def main():
             with torch.cuda.stream(prefetch_stream):
                 H.prepare_network_input(x_t)
         loss = criterion(output, tgt.view(output.size()))
+        if keep is not None:
+            keep["sp_loss"] = loss.detach().clone()
         loss.backward()
         optimizer.step()
         optimizer.zero_grad()
@@ -272,13 +324,13 @@ def main():
                 # beside the SP step's kernels: the wavefront form (the persistent LSTM kernels want every CU to themselves; the
                 # stand-alone AT leg below -- BASELINE config 4 -- runs them)
                 with torch.cuda.stream(at_stream), H.lstm_persistent(args.at_form == "persist"):
-                    at_step()
+                    at_step(keep)
             else:
-                at_step()
+                at_step(keep)
         return loss
 
     probe = None
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         probe = mfma_power_probe(dev)
         print(f"[bench] bare-MFMA probe (f16 32x32x16, random bits): {probe['tflops']:.0f} TFLOP/s "
               f"= {probe['effective_clock_ghz']:.2f} GHz effective", file=sys.stderr, flush=True)
@@ -288,16 +340,17 @@ def main():
     # The timed region: exactly --steps steps between barrier + synchronize on both sides, MAX over ranks.  It is run
     # --repeats times back to back in this process (a 20-step region is 0.6 s and one region per round cannot resolve the
     # sub-1 % changes the round's A/B notes argue about: VERDICT r4): value = the MEDIAN region, all regions reported.
-    def timed_regions():
-        """--repeats regions of exactly --steps steps, each bracketed by barrier + synchronize on both sides, MAX over ranks."""
+    def timed_regions(keep=None):
+        """--repeats regions of exactly --steps steps, each bracketed by barrier + synchronize on both sides, MAX over ranks.
+        ``keep`` is handed to the last step of the last region."""
         regs, last = [], None
-        for _ in range(max(1, args.repeats)):
+        for r in range(repeats):
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            for _ in range(args.steps):
-                last = step()
+            for i in range(args.steps):
+                last = step(keep=keep if r == repeats - 1 and i == args.steps - 1 else None)
             if dist is not None:
                 dist.barrier()
             torch.cuda.synchronize()
@@ -312,12 +365,17 @@ def main():
     def median(regs):
         return sorted(regs)[(len(regs) - 1) // 2]
 
-    regions, loss = timed_regions()
+    kept = {} if args.dump_outputs and rank == 0 else None
+    regions, loss = timed_regions(kept)
     elapsed = median(regions)
     ms_per_step = elapsed / args.steps * 1e3
     frames_per_s = args.batch * world * args.steps / elapsed
     last_loss = loss.item()
     del loss            # the last graph (and its AccumulateGrad nodes, bound to this leg's streams) dies here
+    if kept is not None:
+        # before any other leg steps the model on: the state the timed steps left behind
+        dump_outputs(args.dump_outputs, kept, optimizer, model, opt_at if use_at else None)
+        del kept
 
     roofline = None
     breakdown = None
@@ -329,7 +387,7 @@ def main():
     pcie_ms = {}
     rccl = None
     lf_block = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # Every rank runs these two extra (untimed) steps -- the gradient all-reduce inside step() is a collective --
         # but only rank 0 reports.  Per-kernel HIP-event timing needs the kernels serialised: the multi-stream
         # overlap is switched off so that an event pair brackets exactly one kernel family's launches.
@@ -671,11 +729,11 @@ def main():
         dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     weak = None
-    if rank == 0:
+    if rank == 0 and args.full:
         # Weak-scaling bookkeeping across the driver's back-to-back runs (N = 1, 2, 4, 8 on one node): the N = 1 run leaves its
         # line's key numbers in $TMPDIR, an N > 1 run of the same per-GPU workload on the same host reports its step time against
         # it.  (The driver computes efficiency ITSELF from the per-N values; this block is a convenience for whoever reads one line.)

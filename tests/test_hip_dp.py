@@ -97,7 +97,7 @@ def test_bench_world4_dry_run_every_leg(tmp_path):
     env = _env()
     env["EGAZE_DP_CHECK"] = "1"
     env["TMPDIR"] = str(tmp_path)
-    common = ["--steps", "2", "--warmup", "1", "--repeats", "2", "--batch", "2", "--size", "64", "--no-cpu-baseline"]
+    common = ["--steps", "2", "--warmup", "1", "--repeats", "2", "--batch", "2", "--size", "64", "--no-cpu-baseline", "--full"]
     r1 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--no-roofline"] + common, env=env,
                         capture_output=True, text=True, timeout=900)
     assert r1.returncode == 0, r1.stdout[-3000:] + r1.stderr[-3000:]

@@ -11,6 +11,19 @@ from oracle import egaze_oracle as O
 from oracle import synth
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
+GOLDEN_THREADS = 8          # torch.set_num_threads of tests/golden/make_golden.py
+
+
+@pytest.fixture(autouse=True)
+def golden_threads():
+    """The oracle runs on as many torch-CPU threads as the goldens were written with, whatever the host has: the rounding of
+    a threaded reduction follows the split.  It matters where the exact value is zero -- the biases of late_fusion's convolutions
+    ahead of train-mode BatchNorm have zero gradient, so both sides hold rounding residue (1e-8 ... 1e-6) that agrees only
+    under the same split."""
+    keep = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(keep)
 
 
 def g(name):

@@ -3,7 +3,7 @@
 E=$1; shift
 for v in "$@"; do
   echo "=== $v"
-  env $v python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-f32-leg 2>/dev/null | E=$E python -c "
+  env $v python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-f32-leg 2>/dev/null | E=$E python -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 b=d['kernel_ms_breakdown']

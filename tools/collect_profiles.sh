@@ -7,16 +7,16 @@ O=$R/gpurun_out/profiles_r06
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 # every profiled step is the DEFAULT arithmetic (three products per MAC everywhere): the opt-in-arithmetic leg and the exact-f32 leg are off
-BENCH="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-bwd-leg"
+BENCH="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-bwd-leg"
 
 # 2. rocprofv3 kernel stats, streams on / off (the roofline leg's configuration)
 rm -rf /tmp/ks1 /tmp/ks0
 timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/ks1 -o p -- $BENCH > /dev/null 2>&1
-python $R/tools/prof_summary.py /tmp/ks1 $O/r06_bench_b32_kernel_stats.txt "python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-bwd-leg" > /dev/null
+python $R/tools/prof_summary.py /tmp/ks1 $O/r06_bench_b32_kernel_stats.txt "python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-bwd-leg" > /dev/null
 python $R/tools/trace_mfma.py /tmp/ks1 > $O/r06_exposed_time.txt 2>&1
 python $R/tools/trace_windows.py /tmp/ks1 8 > $O/r06_step_windows.txt 2>&1
 EGAZE_STREAMS=0 timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/ks0 -o p -- $BENCH > /dev/null 2>&1
-python $R/tools/prof_summary.py /tmp/ks0 $O/r06_bench_b32_kernel_stats_streams0.txt "EGAZE_STREAMS=0 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-bwd-leg" > /dev/null
+python $R/tools/prof_summary.py /tmp/ks0 $O/r06_bench_b32_kernel_stats_streams0.txt "EGAZE_STREAMS=0 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-f32-leg --no-bwd-leg" > /dev/null
 
 # 3. HBM traffic per launch (separate --pmc passes), conv fwd + dgrad family and wgrad family
 rm -rf /tmp/pf /tmp/pw
@@ -25,11 +25,11 @@ EGAZE_STREAMS=0 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d /t
 python $R/tools/pmc_traffic.py /tmp/pf /tmp/pw igemm_x3 $O/r06_pmc_traffic_conv_fwd_dgrad.json
 python $R/tools/pmc_traffic.py /tmp/pf /tmp/pw wgrad9_x3,wgrad_ups_x3 $O/r06_pmc_traffic_wgrad.json
 
-# 3b. the default bench line, after the traffic files so that it can quote them (bench.py reads profiles/ and checks
+# 3b. the full bench line, after the traffic files so that it can quote them (bench.py reads profiles/ and checks
 #     the kernel-source hash stamped into them)
 cp $O/r06_pmc_traffic_conv_fwd_dgrad.json $O/r06_pmc_traffic_wgrad.json $R/profiles/
 cd /tmp
-timeout 900 python $R/bench.py > $O/r06_bench_b32.json 2> $O/r06_bench_b32.stderr
+timeout 900 python $R/bench.py --full > $O/r06_bench_b32.json 2> $O/r06_bench_b32.stderr
 
 # 4. SQ / GRBM counters of the conv kernels on three layer shapes
 cd $R
@@ -49,7 +49,7 @@ timeout 900 python tools/cpu_baseline_b32.py 16 > $O/r06_cpu_baseline_b32.txt 2>
 # 11. backward convolutions on two / three MFMA products per MAC: the step, alternating, and the accuracy report
 { for rep in 1 2; do for v in 3 2; do
     echo "--- EGAZE_BWD_PRODUCTS=$v"
-    EGAZE_BWD_PRODUCTS=$v timeout 300 python bench.py --steps 20 --warmup 8 --no-cpu-baseline --no-f32-leg --no-roofline 2>/dev/null | python -c "
+    EGAZE_BWD_PRODUCTS=$v timeout 300 python bench.py --full --steps 20 --warmup 8 --no-cpu-baseline --no-f32-leg --no-roofline 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 print('ms/step %.3f  regions %s' % (d['ms_per_step'], [round(x,3) for x in d['extra']['timed_repeats']['ms_per_step']]))"

@@ -3,7 +3,7 @@
 # Usage (GPU box): bash tools/power_trace.sh <out.txt>
 OUT=$1
 rocm-smi --showmaxpower --showpower --showclocks > $OUT.idle 2>&1
-( python bench.py --steps 300 --warmup 5 --no-cpu-baseline --no-f32-leg --no-roofline > $OUT.bench 2>/dev/null ) &
+( python bench.py --full --steps 300 --warmup 5 --no-cpu-baseline --no-f32-leg --no-roofline > $OUT.bench 2>/dev/null ) &
 BP=$!
 sleep 12
 for i in $(seq 1 12); do
