@@ -72,12 +72,18 @@ class GraphedTrainStep:
     is exactly one eager step.  The first ``warm`` calls run eagerly (real steps: lazy packings, workspaces and helper
     streams come into being), the next one is captured.
 
-    For single-chain models (late_fusion, lstmnet).  The two-stream SP step is NOT capturable this way -- its encoder streams and
+    For single-chain models (late_fusion, lstmnet, the stream pre-training VGG: streamtrain.GraphedStreamStep).  The two-stream
+    SP step is NOT capturable this way -- its encoder streams and
     detached weight-gradient forks do not all rejoin the capturing stream inside the step (ending such a capture crashes inside
     the HIP runtime) -- and has nothing to gain: at batch 32 the host issues its ~700 launches in a third of the device time (§4)."""
 
-    def __init__(self, forward_loss, optimizer, example_inputs: Sequence[torch.Tensor], warm: int = 2):
+    def __init__(self, forward_loss, optimizer, example_inputs: Sequence[torch.Tensor], warm: int = 2,
+                 extra_params: Sequence[torch.Tensor] = ()):
+        """``extra_params``: parameters the step reads but the optimizer does not own (a frozen encoder): their packed weights
+        are baked into the graph too, so an outside write between two replays (tracked by the torch version counter and the
+        fused optimizers' per-parameter epoch) repacks them, and a re-allocation re-captures the step."""
         self.fn, self.opt, self.warm = forward_loss, optimizer, warm
+        self.extra = list(extra_params)
         self.static_in = [t.clone() for t in example_inputs]
         self.graph, self.calls, self.out = None, 0, None
         self.one = torch.ones((), device=self.static_in[0].device)
@@ -107,6 +113,7 @@ class GraphedTrainStep:
             self.opt.step_count = count          # the capture ran the host side of step() without executing anything
             self.graph = g
             self._versions = [p._version for p in self.opt.params]
+            self._extra_sig = self._extra_signature()
             g.replay()
             self.opt.note_replays(1)
         else:
@@ -117,9 +124,22 @@ class GraphedTrainStep:
             if versions != self._versions:
                 H.refresh_packings(self.opt.params, force=True)
                 self._versions = versions
+            if self.extra:
+                sig = self._extra_signature()
+                if sig[1] != self._extra_sig[1]:
+                    # re-allocated (``p.data = ...``): the graph holds the old addresses
+                    self.graph = None
+                    self.calls = self.warm
+                    return self(*inputs)
+                if sig != self._extra_sig:
+                    H.repack_stale(self.extra)
+                    self._extra_sig = sig
             self.graph.replay()
             self.opt.note_replays(1)
         return self.out
+
+    def _extra_signature(self):
+        return ([(p._version, getattr(p, "_egz_epoch", 0)) for p in self.extra], [p.data_ptr() for p in self.extra])
 
     def close(self):
         self.opt.set_capturable(False)

@@ -334,6 +334,21 @@ def refresh_packings(params, force: bool = False) -> int:
     return len(todo)
 
 
+def repack_stale(params) -> int:
+    """Rebuild now, on the current stream and into their existing buffers, every packing of ``params`` (any kind) whose tag went
+    stale: a captured hipGraph bakes the packed buffers in as pointers, so parameters overwritten from outside between two replays
+    (``load_state_dict`` into a frozen encoder) must be repacked before the next replay.  Returns the number of packings rebuilt."""
+    ids = {getattr(p, "_egz_uid", None) for p in params}
+    n = 0
+    for key in [k for k in _PACKED if k[0] in ids]:
+        hit = _PACKED.get(key)
+        w = hit[2]() if hit is not None else None
+        if w is not None and hit[0] != _tag(w):
+            packed_weight(w, key[1], key[2])
+            n += 1
+    return n
+
+
 # ----------------------------------------------------------------------------- gradient sinks
 class GradSink:
     """Where a parameter's gradient lands when the parameter lives in a fused optimizer's flat buffers (optim.FusedAdam):

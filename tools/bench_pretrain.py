@@ -1,0 +1,144 @@
+"""Stream pre-training step (spatialstream.py / temporalstream.py, streamtrain.py) at 224 x 224 on synthetic data: ms per step and
+frames/s, eager and as one captured hipGraph (--hipgraph), the algorithmic TFLOP of the step, and the SP training step's
+frames/s at the same batch for context.  One JSON line per (stream, batch); times are the median of three windows.
+
+    python tools/bench_pretrain.py [--batches 16 32] [--steps 30] [--warmup 5]
+
+Algorithmic FLOP (2 per MAC): encoder forward + decoder forward + decoder data gradient (none for decoder.0, whose input is
+the encoder's output and needs no gradient) + decoder weight gradient; the 1x1 head, BatchNorm, pooling and loss are not
+counted.  The SP step is counted the same way by bench.py; here only its time is reported."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import egaze_amd  # noqa: E402,F401
+from egaze_amd import streamtrain, synthetic  # noqa: E402
+from egaze_amd.floss import floss  # noqa: E402
+from egaze_amd.models.model_SP import model_SP  # noqa: E402
+from egaze_amd.optim import FusedAdam  # noqa: E402
+from egaze_amd.utils import cfg, make_layers  # noqa: E402
+
+
+def conv_flops(model, B, size):
+    """(encoder fwd, decoder fwd, decoder dgrad, decoder wgrad) FLOP of one step at batch B."""
+    def walk(seq, hw, first_dgrad):
+        fwd, dgrad, wgrad, first = 0, 0, 0, True
+        for m in seq.children():
+            if isinstance(m, torch.nn.MaxPool2d):
+                hw //= 2
+            elif isinstance(m, torch.nn.Upsample):
+                hw *= 2
+            elif isinstance(m, torch.nn.Conv2d):
+                f = 2 * B * hw * hw * m.in_channels * m.out_channels * m.kernel_size[0] * m.kernel_size[1]
+                fwd += f
+                wgrad += f
+                if not first or first_dgrad:
+                    dgrad += f
+                first = False
+        return fwd, dgrad, wgrad, hw
+    e_fwd, _, _, hw = walk(model.features, size, False)
+    d_fwd, d_dgrad, d_wgrad, _ = walk(model.decoder, hw, False)
+    return e_fwd, d_fwd, d_dgrad, d_wgrad
+
+
+WINDOWS = []          # ms per step of every timing window, in order (reported with each line)
+
+
+def timed(fn, steps, warmup, windows=3):
+    """Median over ``windows`` back-to-back windows of ``steps`` steps (a single window can catch a clock or allocator event)."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(windows):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            fn()
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3 / steps)
+    WINDOWS.append([round(m, 3) for m in ms])
+    return sorted(ms)[len(ms) // 2]
+
+
+def stream_step_ms(stream, B, size, steps, warmup, graphed):
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    spec = streamtrain.STREAMS[stream]
+    model = streamtrain.StreamVGG(make_layers(cfg['D'], spec['in_channels']), spec['freeze']).to(dev).train()
+    opt = FusedAdam(model.decoder.parameters(), lr=1e-7)
+    crit = floss().to(dev)
+    b = synthetic.sp_batch(B, size, dev, seed=1)
+    x, gt = b[spec['key']], b["gt"]
+    opt.zero_grad()
+    if graphed:
+        step = streamtrain.GraphedStreamStep(model, crit, opt, (x, gt))
+
+        def fn():
+            step(x, gt)
+        ms = timed(fn, steps, max(warmup, 4))          # (2 eager warm-up steps + the capture inside the warm-up)
+        step.close()
+    else:
+        def fn():
+            out = streamtrain.step_forward(model, x)
+            crit(out, gt.view(out.size())).backward()
+            opt.step()
+            opt.zero_grad()
+        ms = timed(fn, steps, warmup)
+    flops = conv_flops(model, B, size)
+    del model, opt, b
+    torch.cuda.empty_cache()
+    return ms, flops
+
+
+def sp_step_ms(B, size, steps, warmup):
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = model_SP(make_layers(cfg['D'], 3), make_layers(cfg['D'], 20)).to(dev).train()
+    opt = FusedAdam(model.parameters(), lr=1e-7)
+    crit = floss().to(dev)
+    b = synthetic.sp_batch(B, size, dev, seed=1)
+
+    def fn():
+        out = model(b["image"], b["flow"])
+        crit(out, b["gt"].view(out.size())).backward()
+        opt.step()
+        opt.zero_grad()
+    ms = timed(fn, steps, warmup)
+    del model, opt, b
+    torch.cuda.empty_cache()
+    return ms
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--batches", type=int, nargs="+", default=[16, 32])
+    p.add_argument("--size", type=int, default=224)
+    p.add_argument("--steps", type=int, default=30)
+    p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--streams", nargs="+", default=["spatial", "temporal"])
+    a = p.parse_args()
+    for B in a.batches:
+        sp_ms = sp_step_ms(B, a.size, a.steps, a.warmup)
+        for stream in a.streams:
+            del WINDOWS[:]
+            eager, flops = stream_step_ms(stream, B, a.size, a.steps, a.warmup, False)
+            graph, _ = stream_step_ms(stream, B, a.size, a.steps, a.warmup, True)
+            tf = sum(flops) / 1e12
+            print(json.dumps({
+                "stream": stream, "batch": B, "size": a.size, "steps": a.steps,
+                "eager_ms_per_step": round(eager, 3), "eager_frames_per_s": round(B * 1e3 / eager, 1),
+                "hipgraph_ms_per_step": round(graph, 3), "hipgraph_frames_per_s": round(B * 1e3 / graph, 1),
+                "tflop_per_step": round(tf, 4), "gflop_per_frame": {k: round(v / B / 1e9, 2) for k, v in zip(
+                    ("encoder_fwd", "decoder_fwd", "decoder_dgrad", "decoder_wgrad"), flops)},
+                "eager_tflops": round(tf / eager * 1e3, 1), "hipgraph_tflops": round(tf / graph * 1e3, 1),
+                "sp_step_ms": round(sp_ms, 3), "sp_frames_per_s": round(B * 1e3 / sp_ms, 1),
+                "windows_ms": {"eager": WINDOWS[0], "hipgraph": WINDOWS[1]}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
