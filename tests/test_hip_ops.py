@@ -1060,7 +1060,7 @@ def test_conv_ops_elementwise_at_the_headline_geometry(C, K, Hh, ups, monkeypatc
     h = H()
     B = 32
     keep = torch.get_num_threads()
-    torch.set_num_threads(min(32, __import__("os").cpu_count() or 1))
+    torch.set_num_threads(min(16, __import__("os").cpu_count() or 1))
     try:
         hin = Hh // 2 if ups else Hh
         x = rnd(B, C, hin, hin, seed=401).clamp_(min=0)                  # post-ReLU-like operand
