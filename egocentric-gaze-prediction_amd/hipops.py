@@ -1834,6 +1834,93 @@ def aae_auc(out: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:
     return res
 
 
+# ----------------------------------------------------------------------------- dataset preparation (ground-truth gaze maps)
+def area_table(ssize: int, dsize: int):
+    """OpenCV's INTER_AREA decimation table for one axis, non-integer scale (computeResizeAreaTab in imgproc/resize.cpp,
+    restated here: cv2 is not a dependency of this package).  -> (ofs int32 [dsize + 1], si int32 [K], alpha float32 [K]):
+    the entries of output index d are [ofs[d], ofs[d + 1]), in OpenCV's order."""
+    import math
+    import numpy as np
+    if not (0 < dsize <= ssize):
+        raise ValueError(f"area_table: INTER_AREA decimation needs 0 < dsize <= ssize (got {ssize} -> {dsize})")
+    scale = 1.0 / (dsize / ssize)
+    ofs, si, alpha = [0], [], []
+    for d in range(dsize):
+        fs1 = d * scale
+        fs2 = fs1 + scale
+        cell = min(scale, ssize - fs1)
+        s1, s2 = math.ceil(fs1), math.floor(fs2)
+        s2 = min(s2, ssize - 1)
+        s1 = min(s1, s2)
+        if s1 - fs1 > 1e-3:
+            si.append(s1 - 1); alpha.append((s1 - fs1) / cell)
+        for s in range(s1, s2):
+            si.append(s); alpha.append(1.0 / cell)
+        if fs2 - s2 > 1e-3:
+            si.append(s2); alpha.append(min(min(fs2 - s2, 1.0), cell) / cell)
+        ofs.append(len(si))
+    return np.array(ofs, np.int32), np.array(si, np.int32), np.array(alpha, np.float32)
+
+
+_AREA_T = {}
+
+
+def _area_tables(device, src_hw, out_hw):
+    key = (torch.device(device).index or 0, tuple(src_hw), tuple(out_hw))
+    hit = _AREA_T.get(key)
+    if hit is None:
+        hit = tuple(tuple(torch.from_numpy(a).to(device) for a in area_table(s, d)) for s, d in zip(src_hw, out_hw))
+        _AREA_T[key] = hit
+    return hit          # ((y ofs, si, alpha), (x ofs, si, alpha))
+
+
+def gaze_gt_maps(rows: torch.Tensor, cols: torch.Tensor, src_hw, sigma: float, out_hw=(224, 224), mode: int = 0,
+                 want_f64: bool = False, want_fullres: bool = False):
+    """Ground-truth gaze maps of the reference's dataset preparation, N frames in one launch (egz_gaze_gt_maps).
+
+    rows, cols: (N,) integer tensors on the GPU, the impulse position of each frame in [0, H) x [0, W) (negative indices
+    already wrapped).  Each map is scipy.ndimage.gaussian_filter(impulse, sigma) over src_hw = (H, W), min-max normalised,
+    times 255 and area-resized to out_hw: mode 0 resizes the float64 map and rounds (data/dataset_preprocessing.py, GTEA
+    Gaze+, cv2.imwrite of a float64 image), mode 1 truncates to uint8 first and resizes with float accumulation
+    (misc/gazedataset_gt.py, GTEA Gaze).  -> (u8 (N, oh, ow), f64 (N, oh, ow) or None, fullres (N, H, W) float64 or None),
+    all on the GPU; the full-resolution maps cost 8 H W bytes each (tests)."""
+    for t, name in ((rows, "rows"), (cols, "cols")):
+        if not t.is_cuda:
+            raise RuntimeError(f"gaze_gt_maps: {name}: expected a HIP ('cuda') tensor -- this package has no CPU path")
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.dim() != 1:
+            raise ValueError(f"gaze_gt_maps: {name} must be a 1-D integer tensor, got {t.dtype} {tuple(t.shape)}")
+    if rows.numel() != cols.numel() or rows.numel() == 0 or rows.device != cols.device:
+        raise ValueError(f"gaze_gt_maps: rows / cols must be non-empty, of one length and on one device "
+                         f"({rows.numel()} vs {cols.numel()})")
+    H, W = (int(v) for v in src_hw)
+    oh, ow = (int(v) for v in out_hw)
+    if mode not in (0, 1):
+        raise ValueError(f"gaze_gt_maps: mode {mode} is neither 0 (GTEA Gaze+) nor 1 (GTEA Gaze)")
+    if not (0 < oh <= H and 0 < ow <= W):
+        raise ValueError(f"gaze_gt_maps: INTER_AREA decimation needs 0 < out <= src (got {(H, W)} -> {(oh, ow)})")
+    if not sigma > 0:
+        raise ValueError(f"gaze_gt_maps: sigma must be positive, got {sigma}")
+    dev = rows.device
+    gw, radius = _gauss_weights(dev, float(sigma))
+    if radius >= min(H, W):
+        raise ValueError(f"gaze_gt_maps: kernel radius {radius} (sigma {sigma}) must be below min(H, W) = {min(H, W)}")
+    pos = torch.stack((rows.to(torch.int64), cols.to(dev, torch.int64)), 1)
+    bad = ((pos[:, 0] < 0) | (pos[:, 0] >= H) | (pos[:, 1] < 0) | (pos[:, 1] >= W)).any()
+    if bool(bad):
+        raise ValueError(f"gaze_gt_maps: impulse positions must lie in [0, {H}) x [0, {W})")
+    pos = pos.to(torch.int32).contiguous()
+    (yo, ys, ya), (xo, xs, xa) = _area_tables(dev, (H, W), (oh, ow))
+    N = pos.shape[0]
+    u8 = torch.empty((N, oh, ow), dtype=torch.uint8, device=dev)
+    f64 = torch.empty((N, oh, ow), dtype=torch.float64, device=dev) if want_f64 else None
+    full = torch.empty((N, H, W), dtype=torch.float64, device=dev) if want_fullres else None
+    check(LIB.egz_gaze_gt_maps(pos.data_ptr(), N, H, W, gw.data_ptr(), radius, xo.data_ptr(), xs.data_ptr(), xa.data_ptr(),
+                               xs.numel(), yo.data_ptr(), ys.data_ptr(), ya.data_ptr(), ys.numel(), mode, oh, ow,
+                               u8.data_ptr(), f64.data_ptr() if f64 is not None else None,
+                               full.data_ptr() if full is not None else None, _stream()), "egz_gaze_gt_maps")
+    return u8, f64, full
+
+
 # ----------------------------------------------------------------------------- input pipeline / AT glue (SURVEY 8f-2, 8f-3)
 _NORM_CONST = {}
 

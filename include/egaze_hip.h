@@ -383,6 +383,17 @@ int egz_adam_step_dev(float* p, const float* g, float* m, float* v, long n, doub
 int egz_aae_auc(const float* out, const float* gt, int B, int H, int W, const double* gw, int R, double dist,
                 double* res, hipStream_t stream);
 
+/* Dataset preparation (data/dataset_preprocessing.py, misc/gazedataset_gt.py): N ground-truth gaze maps rendered from N impulse
+ * positions pos (N, 2) = (row, col) in [0, H) x [0, W): scipy.ndimage.gaussian_filter of the impulse (gw = the 2R + 1 weights
+ * of scipy's 1-D kernel, R < min(H, W), 'reflect'), min-max normalised times 255, then OpenCV's INTER_AREA resize to oh x ow
+ * from host-built tables (x / y: entries [ofs[d], ofs[d + 1]) of (source index, float32 alpha), nx / ny entries in all).
+ * mode 0: double source and accumulation, out_u8 = round-half-even with saturation; mode 1: truncated uint8 source, float
+ * accumulation.  out_f64 (nullable): (N, oh, ow) resized maps; out_full (nullable): (N, H, W) normalised maps.  fp64, no FMA
+ * contraction: bit-identical with scipy + numpy at full resolution. */
+int egz_gaze_gt_maps(const int* pos, int N, int H, int W, const double* gw, int R, const int* xofs, const int* xsi,
+                     const float* xalpha, int nx, const int* yofs, const int* ysi, const float* yalpha, int ny, int mode,
+                     int oh, int ow, unsigned char* out_u8, double* out_f64, double* out_full, hipStream_t stream);
+
 /* torch.cat((f, g), dim=1) of two one-channel maps, the late-fusion stack's input (models/late_fusion.py:19):
  * f, g [B][1][H][W] -> out [B][2][H][W]; 16-byte copies when HW % 4 == 0 and the pointers are 16-byte aligned, 4-byte ones otherwise. */
 int egz_cat2_planes(const float* f, const float* g, float* out, int B, long HW, hipStream_t stream);
