@@ -14,7 +14,7 @@ import torch.nn as nn
 from torch.utils.data import DataLoader
 
 from .data._io import imwrite, resize
-from .data.STdatas import stage_batch
+from .data.STdatas import stage_batch, to_raw_u8
 from . import hipops as H
 from .functions import MSELoss
 from .models.LSTMnet import lstmnet
@@ -507,7 +507,7 @@ class AT():
                 ch.bufs, ch.sig, ch.out = bufs, sig, out
         with torch.no_grad():
             for i, sample in _progress(enumerate(st_loader)):
-                ring[cur].add(sample, cap)
+                ring[cur].add(to_raw_u8(sample, self.device), cap)
                 if len(ring[cur].samples) >= cap:
                     launch(ring[cur])
                     if prev is not None:

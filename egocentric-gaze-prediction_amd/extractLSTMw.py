@@ -96,6 +96,11 @@ def extractw(loader, model, savepath, crop_size=3, device='0', align=False):
                 if not fix:
                     raise RuntimeError('fixation is not processed.')       # extractLSTMw.py:110-111
                 state = TAKEN
+                if 'jpeg_blob' in sample:          # decode='gpu': the host path's normalised fields, decoded on the device
+                    from .data.STdatas import check_decode_status, stage_batch
+                    image, _, gt = stage_batch(sample, dev)
+                    check_decode_status(sample)
+                    sample = dict(sample, image=image, gt=gt.cpu())
                 feat = model(sample['image'].float().to(dev))                      # (1,512,14,14)
                 w = channel_weight(feat, sample['gt'], crop_size, align).cpu()
                 torch.save(w, os.path.join(savepath, 'fix_' + sample['imname'][0][:-4] + '.pth.tar'))
@@ -113,6 +118,7 @@ def extract_LSTM_training_data(save_path='../512w', trained_model='save/best_fus
     model.load_state_dict(own)
     model.to(torch.device('cuda:' + device)).eval()
     for data, sub in ((traindata, 'train'), (valdata, 'test')):
-        loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True)
+        loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
+                            collate_fn=getattr(data, 'collate_fn', None))
         extractw(loader, model, os.path.join(save_path, sub), crop_size, device, align)
     print('Attention weight for training LSTMnet successfully extracted.')

@@ -49,6 +49,9 @@ def build_parser():
     a('--batch_size_sp', type=int, default=8, help='batch size of SP')
     a('--crop_size', type=int, default=3, help='crop size of vgg conv5_3 feature')
     a('--align', action='store_true')
+    # not a reference flag: absent from the namespace unless given, so the parsed defaults stay the reference's 37
+    a('--gpu_decode', action='store_true', default=argparse.SUPPRESS,
+      help="decode the dataset's JPEGs on the GPU (STDataset(decode='gpu')); default: host decode as the reference")
     return p
 
 
@@ -70,7 +73,8 @@ def _at_stage(args, STTrainData, STValData):
         if not args.train_lstm:
             att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data in (STValData, STTrainData):
-            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True),
+            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
+                                        collate_fn=getattr(data, 'collate_fn', None)),
                              args.extract_late_pred_folder, args.extract_late_feat_folder)
 
 
@@ -116,10 +120,11 @@ def main(argv=None):
     listfixsacTrain, listfixsacVal = _split(args.fixsacPath, args.val_name)
     listTrainFiles, listValFiles = _split(args.imagePath, args.val_name)
     print('num of val samples: ', len(listValFiles))
+    decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
     STTrainData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listTrainFiles, listGtFiles,
-                            listfixsacTrain, args.fixsacPath, raw_u8=True)      # bytes over PCIe, normalised on the GPU
+                            listfixsacTrain, args.fixsacPath, raw_u8=True, decode=decode)   # bytes over PCIe, normalised on the GPU
     STValData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
-                          listfixsacVal, args.fixsacPath, raw_u8=True)
+                          listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
     os.makedirs(args.save_path, exist_ok=True)
     if args.train_sp:
         sp = SP(lr=args.lr, loss_save=args.sp_save_img, save_name=args.save_sp, save_path=args.save_path,

@@ -1921,6 +1921,71 @@ def gaze_gt_maps(rows: torch.Tensor, cols: torch.Tensor, src_hw, sigma: float, o
     return u8, f64, full
 
 
+# ----------------------------------------------------------------------------- JPEG decode (data/STdatas.py, decode='gpu')
+JPEG_STATUS = {0: "ok", 1: "corrupt data", 2: "unsupported JPEG", 3: "size differs from the requested output",
+               4: "unreadable JPEG (libjpeg refuses it: bad header or table, no scan)"}
+
+
+def _dev_table(t, dtype, device, name):
+    if isinstance(t, torch.Tensor):
+        if t.dim() != 1:
+            raise ValueError(f"jpeg_decode: {name} must be 1-D, got {tuple(t.shape)}")
+        return t.to(device=device, dtype=dtype, non_blocking=True).contiguous()
+    return torch.tensor(list(t), dtype=dtype).to(device, non_blocking=True)
+
+
+def jpeg_decode(data: torch.Tensor, offsets, out_hw, channels, out: torch.Tensor = None, planes=None, n3: int = None,
+                stages: int = 2):
+    """Baseline JPEG decode of N streams in one call (egz_jpeg_decode), bit-identical with cv2.imread.
+
+    data: uint8 1-D tensor on the GPU, the concatenated files; offsets: N + 1 byte offsets (stream i is data[offsets[i]:
+    offsets[i + 1]]); out_hw = (H, W), the size every stream must have; channels: per stream 1 (cv2.IMREAD_GRAYSCALE: the Y
+    plane of a colour file) or 3 (BGR; a grayscale file is replicated).  Tables may be lists or tensors on either device.
+    -> (u8, status): u8 is ``out`` or a new (N, C, H, W) tensor, C = 3 if any stream asks for colour, else 1; status (N,)
+    int32 on the GPU (JPEG_STATUS).  ``out`` (uint8, contiguous, on the GPU) is read as planes of H x W: stream i fills
+    planes[i] .. planes[i] + channels[i] - 1 (default planes[i] = i * C), so a caller can decode straight into slices of a
+    batch tensor.  n3: number of streams with channels 3 -- counted from ``channels`` when not given (a device sync if the
+    table is on the GPU).  stages=1 stops after the entropy decode (timing only; ``out`` is not written)."""
+    if not isinstance(data, torch.Tensor) or not data.is_cuda:
+        raise RuntimeError("jpeg_decode: data: expected a HIP ('cuda') tensor -- this package has no CPU decode path")
+    if data.dtype != torch.uint8 or data.dim() != 1 or not data.is_contiguous():
+        raise ValueError(f"jpeg_decode: data must be a contiguous 1-D uint8 tensor, got {data.dtype} {tuple(data.shape)}")
+    H, W = (int(v) for v in out_hw)
+    if not (0 < H <= 4096 and 0 < W <= 4096):
+        raise ValueError(f"jpeg_decode: out_hw {(H, W)} outside 1 .. 4096")
+    dev = data.device
+    if n3 is None:
+        ch = channels.cpu() if isinstance(channels, torch.Tensor) else torch.tensor(list(channels))
+        if not bool(((ch == 1) | (ch == 3)).all()):
+            raise ValueError("jpeg_decode: channels must be 1 or 3 per stream")
+        n3 = int((ch == 3).sum())
+    off = _dev_table(offsets, torch.int64, dev, "offsets")
+    chn = _dev_table(channels, torch.int32, dev, "channels")
+    N = chn.numel()
+    if N == 0 or off.numel() != N + 1:
+        raise ValueError(f"jpeg_decode: {N} streams need {N + 1} offsets, got {off.numel()}")
+    if not 0 <= n3 <= N:
+        raise ValueError(f"jpeg_decode: n3={n3} outside [0, {N}]")
+    C = 3 if n3 else 1
+    if out is None:
+        if planes is not None:
+            raise ValueError("jpeg_decode: planes= needs out=")
+        out = torch.empty((N, C, H, W), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() or out.numel() % (H * W) or out.device != dev:
+        raise ValueError(f"jpeg_decode: out must be a contiguous uint8 GPU tensor of whole {H} x {W} planes on {dev}")
+    pl = (torch.arange(N, dtype=torch.int64) * C).to(dev, non_blocking=True) if planes is None else \
+        _dev_table(planes, torch.int64, dev, "planes")
+    if pl.numel() != N:
+        raise ValueError(f"jpeg_decode: {N} streams but {pl.numel()} plane indices")
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    nb = LIB.egz_jpeg_decode_ws_bytes(N, H, W, n3)
+    ws = workspace(nb, dev)
+    check(LIB.egz_jpeg_decode(data.data_ptr(), data.numel(), off.data_ptr(), chn.data_ptr(), pl.data_ptr(), N, H, W,
+                              out.data_ptr(), out.numel() // (H * W), status.data_ptr(), ws.data_ptr(), nb, n3, stages,
+                              _stream()), "egz_jpeg_decode")
+    return out, status
+
+
 # ----------------------------------------------------------------------------- input pipeline / AT glue (SURVEY 8f-2, 8f-3)
 _NORM_CONST = {}
 

@@ -101,6 +101,10 @@ def stage_stream(sample, device, key, prepare=True):
     NHWC-32 re-layout is issued behind the copy (hipops.prepare_network_input), as data.STdatas.stage_batch does for SP."""
     from . import hipops as H
     from .data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
+    if 'jpeg_blob' in sample:                  # decode='gpu': decoded on the device into the raw_u8 layout
+        from .data.STdatas import decode_to_u8
+        image, flow, gt = decode_to_u8(sample, device)
+        sample = {'image': image, 'flow': flow, 'gt': gt}
     x, gt = sample[key], sample['gt']
     if device.type != 'cuda':
         return x.float().to(device), gt.float().to(device)
@@ -248,6 +252,9 @@ def build_parser(stream):
     p.add_argument('--val_name', default='Alireza', required=False)
     p.add_argument('--hipgraph', action='store_true',
                    help='replay every full training batch as one captured hipGraph (default: eager)')
+    # absent from the namespace unless given: the parsed defaults stay the reference's
+    p.add_argument('--gpu_decode', action='store_true', default=argparse.SUPPRESS,
+                   help="decode the dataset's JPEGs on the GPU (STDataset(decode='gpu')); default: host decode as the reference")
     return p
 
 
@@ -272,7 +279,7 @@ def build_model(stream, resume=0, pretrained_model=None):
     return model
 
 
-def make_loaders(args):
+def make_loaders(args, key=None):
     """The reference's file lists and loaders (spatialstream.py:34-63); shuffled / sharded per rank under torch.distributed."""
     from .data.STdatas import STDataset
     listFolders = sorted(os.listdir(args.flowPath))
@@ -284,16 +291,19 @@ def make_loaders(args):
     listTrainFiles = sorted(k for k in os.listdir(args.imagePath) if args.val_name not in k)
     listValFiles = sorted(k for k in os.listdir(args.imagePath) if args.val_name in k)
     print('num of val samples: ', len(listValFiles))
+    decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
     train_data = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listTrainFiles, listGtFiles,
-                           listfixsacTrain, args.fixsacPath, raw_u8=True)       # bytes over PCIe, normalised on the GPU
+                           listfixsacTrain, args.fixsacPath, raw_u8=True, decode=decode)   # bytes over PCIe, normalised on the GPU
     val_data = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
-                         listfixsacVal, args.fixsacPath, raw_u8=True)
+                         listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
+    if key is not None:                    # decode='gpu': only the stream's input and the ground truth are read and decoded
+        train_data.gpu_fields = val_data.gpu_fields = (key, 'gt')
     train_sampler = dp.RankShardSampler(train_data, True, args.batch_size) if dp.world_size() > 1 else None
     val_sampler = dp.RankShardSampler(val_data, False, args.batch_size, pad=False) if dp.world_size() > 1 else None
     train_loader = DataLoader(dataset=train_data, batch_size=args.batch_size, shuffle=train_sampler is None,
-                              sampler=train_sampler, num_workers=0, pin_memory=True)
+                              sampler=train_sampler, num_workers=0, pin_memory=True, collate_fn=train_data.collate_fn)
     val_loader = DataLoader(dataset=val_data, batch_size=args.batch_size, shuffle=False, sampler=val_sampler, num_workers=0,
-                            pin_memory=True)
+                            pin_memory=True, collate_fn=val_data.collate_fn)
     return train_loader, val_loader, train_sampler
 
 
@@ -315,7 +325,7 @@ def main(stream, argv=None):
         torch.cuda.set_device(int(args.device))
         torch.distributed.init_process_group(os.environ.get('EGAZE_DIST_BACKEND', 'nccl'))
     device = torch.device('cuda:' + args.device)
-    train_loader, val_loader, train_sampler = make_loaders(args)
+    train_loader, val_loader, train_sampler = make_loaders(args, spec['key'])
     model = build_model(stream, args.resume, args.pretrained_model)
     model.to(device)
     print('done!')

@@ -394,6 +394,18 @@ int egz_gaze_gt_maps(const int* pos, int N, int H, int W, const double* gw, int 
                      const float* xalpha, int nx, const int* yofs, const int* ysi, const float* yalpha, int ny, int mode,
                      int oh, int ow, unsigned char* out_u8, double* out_f64, double* out_full, hipStream_t stream);
 
+/* Baseline JPEG decode of N streams in one call (data/STdatas.STDataset(decode='gpu'), csrc/jpeg_decode.hip): stream i is
+ * data[offsets[i], offsets[i + 1]) and is decoded into the channels[i] (1 or 3) uint8 planes of H x W starting at plane
+ * planes[i] of out (out_planes planes in all), bit-identical with libjpeg-turbo's default decode (cv2.imread): BGR for colour,
+ * the Y plane for a grayscale request of a colour file, replicated planes for a colour request of a grayscale file.
+ * status[i]: 0 ok, 1 corrupt data in the scan (decoded with libjpeg's zero padding), 2 unsupported, 3 size differs from
+ * H x W, 4 a file libjpeg refuses (bad header or table, no scan; cv2.imread returns None).  2 / 3 / 4 write nothing.  n3 = number of streams with channels 3,
+ * ws = egz_jpeg_decode_ws_bytes(N, H, W, n3) bytes.  stages: 2 = full decode, 1 = header + entropy decode only (timing). */
+size_t egz_jpeg_decode_ws_bytes(int N, int H, int W, int n3);
+int egz_jpeg_decode(const unsigned char* data, long data_len, const long* offsets, const int* channels, const long* planes,
+                    int N, int H, int W, unsigned char* out, long out_planes, int* status, void* ws, size_t ws_bytes,
+                    int n3, int stages, hipStream_t stream);
+
 /* torch.cat((f, g), dim=1) of two one-channel maps, the late-fusion stack's input (models/late_fusion.py:19):
  * f, g [B][1][H][W] -> out [B][2][H][W]; 16-byte copies when HW % 4 == 0 and the pointers are 16-byte aligned, 4-byte ones otherwise. */
 int egz_cat2_planes(const float* f, const float* g, float* out, int B, long HW, hipStream_t stream);
