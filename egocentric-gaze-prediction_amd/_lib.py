@@ -130,6 +130,9 @@ SIGNATURES = {
     "egz_aae_auc": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_double, P, S]),
     "egz_gaze_gt_maps": (c_int, [P, c_int, c_int, c_int, P, c_int, P, P, P, c_int, P, P, P, c_int, c_int, c_int, c_int,
                                  P, P, P, S]),
+    "egz_resize_linear_u8": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, S]),
+    "egz_heatmap_overlay": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P, P, P, P, P, S]),
+    "egz_cell_argmax_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, S]),
     "egz_jpeg_decode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "egz_jpeg_decode": (c_int, [P, c_long, P, P, P, c_int, c_int, c_int, P, c_long, P, P, c_size_t, c_int, c_int, S]),
     "egz_adam_step": (c_int, [P, P, P, P, c_long, c_double, c_double, c_double, c_double, c_int, c_double, P, S]),

@@ -33,6 +33,22 @@ def imwrite(path, arr):
         Image.fromarray(arr).save(path)
 
 
+def imwrite_bgr(path, arr, quality=95):
+    """cv2.imwrite of a (H, W, 3) BGR or (H, W) uint8 image; without cv2, PIL with the channels turned to RGB and, for JPEG,
+    cv2's default quality (95)."""
+    try:
+        import cv2
+        cv2.imwrite(path, arr)
+        return
+    except ImportError:
+        from PIL import Image
+        im = Image.fromarray(np.ascontiguousarray(arr[:, :, ::-1]) if arr.ndim == 3 else arr)
+        if path.lower().endswith((".jpg", ".jpeg")):
+            im.save(path, quality=quality)
+        else:
+            im.save(path)
+
+
 def resize(arr, size):
     try:
         import cv2

@@ -394,6 +394,21 @@ int egz_gaze_gt_maps(const int* pos, int N, int H, int W, const double* gw, int 
                      const float* xalpha, int nx, const int* yofs, const int* ysi, const float* yalpha, int ny, int mode,
                      int oh, int ow, unsigned char* out_u8, double* out_f64, double* out_full, hipStream_t stream);
 
+/* Feature visualisation (vis_features.py, csrc/vis_overlay.hip).  OpenCV's INTER_LINEAR resize of N 8-bit images (C = 1 or 3,
+ * planar (C, H, W) or interleaved (H, W, C)) from host-built 11-bit tables (hipops.linear_table): xofs[dw] clamped source
+ * columns, xalpha[2 dw]; yofs[dh] unclamped source rows, yalpha[2 dh].  Integer arithmetic only, bit-identical with OpenCV's
+ * fixed-point path.  The overlay chain resizes M maps (h x w) to H x W with the same tables, looks each value up in a 256 x 3 BGR
+ * table and blends it over frame frame_index[m] of the (F, 3, H, W) BGR planes as rint(fl64(h * 0.3) + fl64(i * 0.5)) into
+ * (M, H, W, 3) BGR bytes.  cell_argmax: per (H, W) byte map, the row-major index of the first maximal exact sum over the
+ * (H / cell) x (W / cell) cells. */
+int egz_resize_linear_u8(const unsigned char* src, int N, int C, int sh, int sw, int dh, int dw, int interleaved,
+                         const int* xofs, const short* xalpha, const int* yofs, const short* yalpha, unsigned char* dst,
+                         hipStream_t stream);
+int egz_heatmap_overlay(const unsigned char* maps, int M, int h, int w, const int* frame_index, const unsigned char* frames,
+                        int F, int H, int W, const unsigned char* lut, const int* xofs, const short* xalpha, const int* yofs,
+                        const short* yalpha, unsigned char* out, hipStream_t stream);
+int egz_cell_argmax_u8(const unsigned char* gt, int N, int H, int W, int cell, int* out, hipStream_t stream);
+
 /* Baseline JPEG decode of N streams in one call (data/STdatas.STDataset(decode='gpu'), csrc/jpeg_decode.hip): stream i is
  * data[offsets[i], offsets[i + 1]) and is decoded into the channels[i] (1 or 3) uint8 planes of H x W starting at plane
  * planes[i] of out (out_planes planes in all), bit-identical with libjpeg-turbo's default decode (cv2.imread): BGR for colour,
