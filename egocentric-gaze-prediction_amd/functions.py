@@ -320,7 +320,8 @@ class ConvReLU(torch.autograd.Function):
     chains, models/model_SP.py:13-29).  Then this node's data gradient IS the gradient w.r.t. that block's post-ReLU output,
     and the ReLU mask of the block below (input > 0), its bias gradient (column sums of the masked gradient) and the abs-max
     of the result are produced in the epilogue of this node's dgrad kernel (hipops.conv3x3_dgrad_masked); the gradient
-    tensor handed down carries them (``_egz_premasked``), and the block below skips its own ReLU-backward pass."""
+    tensor handed down carries them (``_egz_premasked``, with the tensor's version: a gradient written in place on the way
+    down is stale, as for ``_egz_bnsums``), and the block below skips its own ReLU-backward pass."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, ups, relu_below=False):
@@ -343,11 +344,15 @@ class ConvReLU(torch.autograd.Function):
         dx = dw = db = None
         sbias = H.grad_sink(bias, ng[2])
         pre = getattr(dout, "_egz_premasked", None)
+        if pre is not None and pre[2] != dout._version:
+            # written in place since the kernel above produced it (a tensor hook, an accumulation): the mask may no longer hold
+            # and the stat rows and the abs-max describe the old values -- this block takes its own ReLU-backward pass
+            pre = None
         bias_stat = None
         if pre is not None and tuple(dout.shape) == (y.shape[0], K, y.shape[1], y.shape[2]):
             # the block above already applied this block's ReLU mask in its dgrad epilogue
             dy = to_nhwc(dout)
-            stat, am = pre
+            stat, am, _ = pre
             H.MASK_FUSE_STATS["consumed"] += 1
             if am is not None:
                 dy._egz_absmax = am
@@ -373,7 +378,7 @@ class ConvReLU(torch.autograd.Function):
             if relu_below and st and H.MASK_FUSE and C % 64 == 0:
                 dxn, stat, am = H.conv3x3_dgrad_masked(dy, wp, C, dt, xin, ups)
                 d = from_nhwc(dxn)
-                d._egz_premasked = (stat, am if H._want_absmax() else None)
+                d._egz_premasked = (stat, am if H._want_absmax() else None, d._version)
                 return d
             if ups:       # gradient w.r.t. the low-res input directly (4x4 / stride-2 gather over dy)
                 return from_nhwc(H.conv3x3_ups_dgrad(dy, wp, C, dtype=dt, streamed=st))
@@ -485,7 +490,7 @@ class HeadSigmoid(torch.autograd.Function):
             dx, dw, db, stat, am = H.conv1x1_sigmoid_bwd_masked(xin, weight.detach(), out, dout.contiguous(), out_dw=sw,
                                                                 out_db=sb)
             d = from_nhwc(dx)
-            d._egz_premasked = (stat, am if H._want_absmax() else None)
+            d._egz_premasked = (stat, am if H._want_absmax() else None, d._version)
             return d, _finish(weight, sw, dw if ng[1] else None), _finish(bias, sb, db if ng[2] else None), None
         dx, dw, db = H.conv1x1_sigmoid_bwd(xin, weight.detach(), out, dout.contiguous(), need_dx=ng[0], out_dw=sw,
                                            out_db=sb)
