@@ -135,6 +135,9 @@ SIGNATURES = {
     "egz_cell_argmax_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, S]),
     "egz_jpeg_decode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "egz_jpeg_decode": (c_int, [P, c_long, P, P, P, c_int, c_int, c_int, P, c_long, P, P, c_size_t, c_int, c_int, S]),
+    "egz_jpeg_encode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "egz_jpeg_encode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, c_int, S]),
+    "egz_jpeg_encode_write": (c_int, [P, c_size_t, c_int, c_int, c_int, c_int, P, c_long, P, P, P, P, S]),
     "egz_adam_step": (c_int, [P, P, P, P, c_long, c_double, c_double, c_double, c_double, c_int, c_double, P, S]),
     "egz_adam_step_dev": (c_int, [P, P, P, P, c_long, c_double, c_double, c_double, c_double, P, c_double, P, S]),
 }

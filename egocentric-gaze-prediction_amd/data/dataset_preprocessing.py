@@ -9,7 +9,9 @@ For every gaze log ``<gazePath>/<video>_gaze.txt`` it writes, with the reference
 The reference's map code (kept in a string literal there, which the README points users to) filters a 960 x 1280 float64
 impulse with scipy's gaussian_filter(sigma 70), min-max normalises it, multiplies by 255, area-resizes it with cv2 and writes
 it with cv2.imwrite; here all maps of a video are rendered in one ``hipops.gaze_gt_maps`` launch (bit-identical arithmetic,
-see csrc/gaze_gt.hip) and read back once, while a thread pool encodes the maps and copies the frames.
+see csrc/gaze_gt.hip) and read back once, while a thread pool encodes the maps and copies the frames.  With ``--gpu-encode``
+the maps stay on the device, ``hipops.jpeg_encode`` makes the JPEG files of a whole video in one call (byte-identical with
+the quality-95 files libjpeg-turbo writes), the bytes are read back once and the pool only writes files and copies frames.
 
     python -m egaze_amd.data.dataset_preprocessing --gazePath gtea_gaze --flowPath gtea_imgflow \\
         --imagePath gtea_images --gtPath gtea_gts --fixsacPath fixsac
@@ -110,15 +112,32 @@ def gt_name(video, img, gt_format):
     return video + '_gt_' + img
 
 
-def render_maps(gazex, gazey, sigma=70.0, device='cuda'):
-    """uint8 (N, 224, 224) maps of the frames (gazex[i], gazey[i]) on the host: one launch, one read-back."""
+def write_bytes(path, data):
+    with open(path, 'wb') as fh:
+        fh.write(data)
+
+
+def encode_maps_gpu(u8, quality=95):
+    """JPEG files of the uint8 (N, H, W) maps ``u8`` on the GPU: one hipops.jpeg_encode call, one read-back of the bytes.
+    -> list of N uint8 arrays (views of one buffer), each a complete file."""
+    from .. import hipops
+    data, offsets, status = hipops.jpeg_encode(u8, quality=quality)
+    buf, off = data.cpu().numpy(), offsets.cpu().tolist()
+    if int(status.abs().max()):
+        raise RuntimeError(f"jpeg_encode: status {sorted(set(status.cpu().tolist()))}")
+    return [buf[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+def render_maps(gazex, gazey, sigma=70.0, device='cuda', host=True):
+    """uint8 (N, 224, 224) maps of the frames (gazex[i], gazey[i]) on the host: one launch, one read-back.  host=False
+    leaves them on the device as a tensor."""
     import torch
     from .. import hipops
     H, W = GTEA_SIZE
     rows = torch.tensor([impulse_index(y, H) for y in gazey], dtype=torch.int32)
     cols = torch.tensor([impulse_index(x, W) for x in gazex], dtype=torch.int32)
     u8, _, _ = hipops.gaze_gt_maps(rows.to(device), cols.to(device), GTEA_SIZE, sigma, GT_SIZE, mode=0)
-    return u8.cpu().numpy()
+    return u8.cpu().numpy() if host else u8
 
 
 def process_video(f, args, pool, device='cuda'):
@@ -137,6 +156,12 @@ def process_video(f, args, pool, device='cuda'):
         for i in range(1, len(nframe)):
             futs.append(pool.submit(shutil.copyfile, os.path.join(args.flowPath, video, ims[i]),
                                     os.path.join(args.imagePath, video + '_' + ims[i])))
+    if getattr(args, 'gpu_encode', False):
+        files = encode_maps_gpu(render_maps(gazex[1:], gazey[1:], args.sigma, device, host=False))
+        for i in range(1, len(nframe)):
+            futs.append(pool.submit(write_bytes, os.path.join(args.gtPath, gt_name(video, ims[i], args.gt_format)),
+                                    files[i - 1]))
+        return futs
     maps = render_maps(gazex[1:], gazey[1:], args.sigma, device)
     for i in range(1, len(nframe)):
         futs.append(pool.submit(write_map, os.path.join(args.gtPath, gt_name(video, ims[i], args.gt_format)), maps[i - 1]))
@@ -155,6 +180,8 @@ def build_parser():
     a('--fixsac-only', action='store_true', help="write the label files only (the reference's live code)")
     a('--no-copy-images', action='store_true', help="do not copy the RGB frames")
     a('--gt-format', choices=('jpg', 'png'), default='jpg', help="jpg: the reference's names, quality 95; png: lossless")
+    a('--gpu-encode', action='store_true', help="encode the JPEG maps on the GPU (hipops.jpeg_encode, quality 95); the "
+                                                "workers only write files")
     a('--sigma', type=float, default=70.0, help="Gaussian sigma in pixels of the 960 x 1280 gaze frame")
     a('--workers', type=int, default=8, help="threads encoding maps and copying frames")
     a('--device', default='cuda', help="torch device the maps are rendered on")
@@ -162,9 +189,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     if args.workers < 1:
         raise SystemExit("--workers must be at least 1")
+    if args.gpu_encode and args.gt_format != 'jpg':
+        parser.error("--gpu-encode writes JPEG maps: it cannot be combined with --gt-format png")
     os.makedirs(args.fixsacPath, exist_ok=True)
     if not args.fixsac_only:
         os.makedirs(args.gtPath, exist_ok=True)

@@ -1986,6 +1986,93 @@ def jpeg_decode(data: torch.Tensor, offsets, out_hw, channels, out: torch.Tensor
     return out, status
 
 
+# ----------------------------------------------------------------------------- JPEG encode (--gpu-encode / --gpu_encode)
+JPEG_ENCODE_STATUS = {0: "ok", 1: "the output slot is smaller than the file (nothing of it was written)"}
+_SUBSAMPLING = {"420": 420, "4:2:0": 420, 420: 420, 2: 420}
+
+
+def _jpeg_encode_args(images, quality, layout, subsampling):
+    if not isinstance(images, torch.Tensor) or not images.is_cuda:
+        raise RuntimeError("jpeg_encode: images: expected a HIP ('cuda') tensor -- this package has no CPU path")
+    if images.dtype != torch.uint8:
+        raise ValueError(f"jpeg_encode: images must be uint8, got {images.dtype}")
+    if layout is None:
+        layout = "bgr" if images.dim() == 4 else "gray"
+    if layout not in ("gray", "bgr"):
+        raise ValueError(f"jpeg_encode: layout {layout!r}: 'gray' (N, H, W) or 'bgr' (N, H, W, 3) -- RGB, planar colour, "
+                         "CMYK and 12-bit input are not built")
+    if (layout == "gray" and images.dim() != 3) or (layout == "bgr" and (images.dim() != 4 or images.shape[3] != 3)):
+        raise ValueError(f"jpeg_encode: images of shape {tuple(images.shape)} do not match layout {layout!r}: "
+                         "'gray' is (N, H, W), 'bgr' is (N, H, W, 3)")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_encode: quality {quality!r} outside 1 .. 100")
+    if subsampling not in _SUBSAMPLING:
+        raise ValueError(f"jpeg_encode: subsampling {subsampling!r}: only '420' is built (Pillow's and cv2's default); "
+                         "'444' and '422' are not")
+    N, H, W = (int(v) for v in images.shape[:3])
+    if not (0 < H <= 4096 and 0 < W <= 4096):
+        raise ValueError(f"jpeg_encode: images of {H} x {W}: height and width must be 1 .. 4096")
+    if not 0 < N <= 65535:
+        raise ValueError(f"jpeg_encode: images holds {N} images: 1 .. 65535 per call")
+    return images.contiguous(), N, H, W, (3 if layout == "bgr" else 1), _SUBSAMPLING[subsampling]
+
+
+def _jpeg_encode_scan(img, N, H, W, C, quality, sub, stages=4):
+    """First half of the encode: -> (workspace, its size, needed lengths (N,) int64 on the GPU)."""
+    nb = LIB.egz_jpeg_encode_ws_bytes(N, H, W, C)
+    ws = torch.empty(nb, dtype=torch.uint8, device=img.device)        # hundreds of MB for a large batch: not the shared scratch
+    needed = torch.zeros(N, dtype=torch.int64, device=img.device)
+    check(LIB.egz_jpeg_encode(img.data_ptr(), N, H, W, C, quality, sub, ws.data_ptr(), nb, needed.data_ptr(), stages,
+                              _stream()), "egz_jpeg_encode")
+    return ws, nb, needed
+
+
+def jpeg_encode(images: torch.Tensor, quality: int = 95, layout: str = None, subsampling="420"):
+    """Baseline JPEG encode of N images in one call (egz_jpeg_encode), every file byte-identical with Pillow's
+    Image.save(format="JPEG", quality=quality) -- libjpeg-turbo's defaults, which cv2.imwrite runs too.
+
+    images: uint8 on the GPU, (N, H, W) grey (layout 'gray') or (N, H, W, 3) BGR (layout 'bgr', written as YCbCr 4:2:0);
+    layout defaults to the one the shape implies.  -> (data, offsets, status): data a 1-D uint8 GPU tensor of the N complete
+    files one after the other, offsets N + 1 int64 on the GPU (file i is data[offsets[i]:offsets[i + 1]]), status (N,) int32
+    on the GPU (JPEG_ENCODE_STATUS; all 0 here) -- what jpeg_decode takes as (data, offsets).  The N lengths are read back
+    once, between the entropy coding and the final write, to allocate the exact output."""
+    img, N, H, W, C, sub = _jpeg_encode_args(images, quality, layout, subsampling)
+    ws, nb, needed = _jpeg_encode_scan(img, N, H, W, C, quality, sub)
+    offsets = torch.zeros(N + 1, dtype=torch.int64)
+    torch.cumsum(needed.cpu(), 0, out=offsets[1:])                    # the one read-back
+    data = torch.empty(int(offsets[-1]), dtype=torch.uint8, device=img.device)
+    off = offsets.to(img.device)
+    lengths = torch.empty(N, dtype=torch.int64, device=img.device)
+    status = torch.empty(N, dtype=torch.int32, device=img.device)
+    check(LIB.egz_jpeg_encode_write(ws.data_ptr(), nb, N, H, W, C, data.data_ptr(), data.numel(), off.data_ptr(),
+                                    needed.data_ptr(), lengths.data_ptr(), status.data_ptr(), _stream()),
+          "egz_jpeg_encode_write")
+    return data, off, status
+
+
+def jpeg_encode_into(images: torch.Tensor, out: torch.Tensor, slot_offsets, slot_capacity, quality: int = 95,
+                     layout: str = None, subsampling="420"):
+    """jpeg_encode into a buffer of the caller's, without the read-back: file i goes to out[slot_offsets[i]:] if it fits in
+    slot_capacity[i] bytes (and in ``out``).  -> (lengths, status), both (N,) on the GPU: the length every file needs, and
+    0, or 1 where the slot was too small -- then nothing of that file is written."""
+    img, N, H, W, C, sub = _jpeg_encode_args(images, quality, layout, subsampling)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda:
+        raise RuntimeError("jpeg_encode_into: out: expected a HIP ('cuda') tensor -- this package has no CPU path")
+    if out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != img.device or not out.numel():
+        raise ValueError(f"jpeg_encode_into: out must be a non-empty contiguous 1-D uint8 tensor on {img.device}")
+    so = _dev_table(slot_offsets, torch.int64, img.device, "slot_offsets")
+    sc = _dev_table(slot_capacity, torch.int64, img.device, "slot_capacity")
+    if so.numel() != N or sc.numel() != N:
+        raise ValueError(f"jpeg_encode_into: {N} images need {N} slot_offsets and {N} slot_capacity entries, got "
+                         f"{so.numel()} and {sc.numel()}")
+    ws, nb, _ = _jpeg_encode_scan(img, N, H, W, C, quality, sub)
+    lengths = torch.empty(N, dtype=torch.int64, device=img.device)
+    status = torch.empty(N, dtype=torch.int32, device=img.device)
+    check(LIB.egz_jpeg_encode_write(ws.data_ptr(), nb, N, H, W, C, out.data_ptr(), out.numel(), so.data_ptr(), sc.data_ptr(),
+                                    lengths.data_ptr(), status.data_ptr(), _stream()), "egz_jpeg_encode_write")
+    return lengths, status
+
+
 # ----------------------------------------------------------------------------- input pipeline / AT glue (SURVEY 8f-2, 8f-3)
 _NORM_CONST = {}
 

@@ -73,14 +73,14 @@ def impulse_indices(interpx, interpy):
     return rows, cols
 
 
-def render_maps(interpx, interpy, sigma=35.0, device='cuda'):
-    """uint8 (N, 224, 224) maps of a whole track: one launch, one read-back."""
+def render_maps(interpx, interpy, sigma=35.0, device='cuda', host=True):
+    """uint8 (N, 224, 224) maps of a whole track: one launch, one read-back (host=False: left on the device)."""
     import torch
     from .. import hipops
     rows, cols = impulse_indices(interpx, interpy)
     u8, _, _ = hipops.gaze_gt_maps(torch.from_numpy(rows).to(device), torch.from_numpy(cols).to(device), FRAME_SIZE, sigma,
                                    GT_SIZE, mode=1)
-    return u8.cpu().numpy()
+    return u8.cpu().numpy() if host else u8
 
 
 def process_track(t, args, pool):
@@ -94,9 +94,12 @@ def process_track(t, args, pool):
             fh.write(str(v) + '\n')
     if args.gt is None:
         return []
-    from ..data.dataset_preprocessing import write_map
+    from ..data.dataset_preprocessing import encode_maps_gpu, write_bytes, write_map
     out = os.path.join(args.gt, txtname)
     os.makedirs(out, exist_ok=True)
+    if getattr(args, 'gpu_encode', False):
+        files = encode_maps_gpu(render_maps(interpx, interpy, args.sigma, args.device, host=False))
+        return [pool.submit(write_bytes, os.path.join(out, 'gt_%05d.jpg' % j), files[j]) for j in range(len(files))]
     maps = render_maps(interpx, interpy, args.sigma, args.device)
     return [pool.submit(write_map, os.path.join(out, 'gt_%05d.jpg' % j), maps[j]) for j in range(len(maps))]
 
@@ -107,6 +110,8 @@ def build_parser():
     a('--gazePath', default='gazepositions', help="folder of <name>.txt gaze tracks (x y per frame)")
     a('--fixationPath', default='fixations', help="output folder of <name>_fixation.txt")
     a('--gt', default=None, metavar='DIR', help="also write DIR/<name>/gt_%%05d.jpg maps (rendered on the GPU)")
+    a('--gpu-encode', action='store_true', help="encode the maps on the GPU (hipops.jpeg_encode, quality 95); the workers "
+                                                "only write files")
     a('--sigma', type=float, default=35.0, help="Gaussian sigma in pixels of the 480 x 640 frame")
     a('--workers', type=int, default=8, help="threads encoding maps")
     a('--device', default='cuda', help="torch device the maps are rendered on")
@@ -114,9 +119,12 @@ def build_parser():
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
     if args.workers < 1:
         raise SystemExit("--workers must be at least 1")
+    if args.gpu_encode and args.gt is None:
+        parser.error("--gpu-encode needs --gt DIR: without it no maps are written")
     os.makedirs(args.fixationPath, exist_ok=True)
     pending = []
     with ThreadPoolExecutor(max_workers=args.workers) as pool:

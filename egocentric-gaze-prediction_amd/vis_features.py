@@ -12,7 +12,8 @@ model call, ``torch.cat`` of windows of different shapes); the meaning pinned he
 Device side: the model_SP forward (eval, no_grad) with features_s hooked, the gt cell (egz_cell_argmax_u8), the window means
 (egz_window_mean), the weighted maps (egz_weighted_minmax), the uint8 truncation, the LSTM (lstmnet, T = B at batch 1, state
 carried across batches) and every overlay of a batch in ONE egz_heatmap_overlay launch, read back once into pinned memory.
-Only the file writing runs on the host.
+Only the file writing runs on the host; with ``--gpu_encode`` the JPEG encoding of the overlays and the gaze map runs on the
+device too (hipops.jpeg_encode, quality 95, byte-identical files) and the host writes the bytes.
 
     python -m egaze_amd.vis_features --flowPath ../gtea_imgflow --imagePath ../gtea_images --gtPath ../gtea_gts \\
         --fixsacPath ../fixsac --trained_model save/best_fusion.pth.tar --trained_lstm save/valbest_lstm.pth.tar \\
@@ -81,13 +82,27 @@ class _Pinned:
         return dst
 
 
-def vis_features(st_loader, model, modelw, savefolder, first=100, last=1000, all_frames=False, lut=None, writer=None):
+def _is_jpeg(name):
+    return name.lower().endswith(('.jpg', '.jpeg'))
+
+
+def _write_bytes(path, data):
+    with open(path, 'wb') as fh:
+        fh.write(data)
+
+
+def vis_features(st_loader, model, modelw, savefolder, first=100, last=1000, all_frames=False, lut=None, writer=None,
+                 gpu_encode=False):
     """Visualise batches first .. last of ``st_loader`` (the reference's ``i < 100`` / ``i > 1000`` window) into
     ``savefolder``.  The loader must deliver bytes: an ``STDataset(raw_u8=True)`` or ``decode='gpu'`` loader, frames of
     224 x 224.  model: a model_SP (its features_s output is hooked); modelw: an lstmnet.  Row 0 of each batch is written, as in the
     reference; ``all_frames`` writes every row.  lut: (256, 3) uint8 BGR colormap (default hipops.jet_lut).  writer:
-    callable (path, uint8 array) -- default cv2.imwrite, or PIL at JPEG quality 95."""
+    callable (path, uint8 array) -- default cv2.imwrite, or PIL at JPEG quality 95.  gpu_encode: images whose name ends in
+    .jpg / .jpeg are encoded on the device (hipops.jpeg_encode, quality 95) and written as bytes; others go to the default
+    writer.  A ``writer`` receives arrays, so it cannot be combined with gpu_encode."""
     from . import hipops as H
+    if gpu_encode and writer is not None:
+        raise ValueError("vis_features: gpu_encode writes encoded files itself; it cannot be combined with writer=")
     dev = next(model.parameters()).device
     if dev.type != 'cuda':
         raise RuntimeError("vis_features: the model must live on a HIP device -- this package has no CPU path")
@@ -104,13 +119,13 @@ def vis_features(st_loader, model, modelw, savefolder, first=100, last=1000, all
     seen = []
     handle = model.features_s.register_forward_hook(lambda m, i, o: seen.append(o))
     try:
-        _run(st_loader, model, modelw, savefolder, first, last, all_frames, lut, writer, dev, seen)
+        _run(st_loader, model, modelw, savefolder, first, last, all_frames, lut, writer, dev, seen, gpu_encode)
     finally:
         handle.remove()
     H.lstm_persist_check()
 
 
-def _run(st_loader, model, modelw, savefolder, first, last, all_frames, lut, writer, dev, seen):
+def _run(st_loader, model, modelw, savefolder, first, last, all_frames, lut, writer, dev, seen, gpu_encode=False):
     from . import hipops as H
     from .functions import to_nhwc
     pinned = _Pinned()
@@ -148,14 +163,28 @@ def _run(st_loader, model, modelw, savefolder, first, last, all_frames, lut, wri
             maps = [(255 * H.weighted_minmax(feat, w)).to(torch.uint8) for _, w in weights]   # np.uint8(255 * x)
             sel = torch.stack([m[b] for m in maps for b in rows]).contiguous()
             ov = H.heatmap_overlay(sel, image, [b for _ in maps for b in rows], lut)
-            ov_h = pinned.take(ov)
-            gaze_h = gt[rows].reshape(len(rows), *FRAME_HW).cpu()
+            names = sample['imname']
+            enc = gpu_encode and all(_is_jpeg(names[b]) for b in rows)
+            if enc:
+                ov_j = H.jpeg_encode(ov, quality=95)
+                gaze_j = H.jpeg_encode(gt[rows].reshape(len(rows), *FRAME_HW), quality=95)
+            else:
+                ov_h = pinned.take(ov)
+                gaze_h = gt[rows].reshape(len(rows), *FRAME_HW).cpu()
             # the recurrence: the batch's rows are a T = B sequence at batch 1, the state carried over from the previous batch
             hidden = repackage_hidden(hidden)
             out, hidden = modelw(chn_weight.unsqueeze(1), hidden)         # (B, 1, 512)
             pred = out.reshape(B, -1)
             torch.cuda.current_stream().synchronize()
-            names = sample['imname']
+            if enc:
+                (ov_b, ov_o), (gz_b, gz_o) = ((j[0].cpu().numpy(), j[1].cpu().tolist()) for j in (ov_j, gaze_j))
+                for k, (prefix, _) in enumerate(weights):
+                    for j, b in enumerate(rows):
+                        m = k * len(rows) + j
+                        _write_bytes(os.path.join(savefolder, prefix + names[b]), ov_b[ov_o[m]:ov_o[m + 1]])
+                for j, b in enumerate(rows):
+                    _write_bytes(os.path.join(savefolder, 'gaze_' + names[b]), gz_b[gz_o[j]:gz_o[j + 1]])
+                continue
             for k, (prefix, _) in enumerate(weights):
                 for j, b in enumerate(rows):
                     writer(os.path.join(savefolder, prefix + names[b]), ov_h[k * len(rows) + j].numpy())
@@ -189,6 +218,7 @@ def main(argv=None):
     p.add_argument('--last', type=int, default=1000)
     p.add_argument('--all_frames', action='store_true')
     p.add_argument('--gpu_decode', action='store_true', help="decode the JPEG frames on the GPU (STDataset(decode='gpu'))")
+    p.add_argument('--gpu_encode', action='store_true', help="encode the written JPEGs on the GPU (hipops.jpeg_encode)")
     p.add_argument('--device', default='0', help='GPU index')
     args = p.parse_args(argv)
 
@@ -210,7 +240,8 @@ def main(argv=None):
     _load_into(lstm, args.trained_lstm)
     lstm.to(device)
     os.makedirs(args.savefolder, exist_ok=True)
-    vis_features(loader, model, lstm, args.savefolder, first=args.first, last=args.last, all_frames=args.all_frames)
+    vis_features(loader, model, lstm, args.savefolder, first=args.first, last=args.last, all_frames=args.all_frames,
+                 gpu_encode=args.gpu_encode)
 
 
 if __name__ == '__main__':

@@ -421,6 +421,21 @@ int egz_jpeg_decode(const unsigned char* data, long data_len, const long* offset
                     int N, int H, int W, unsigned char* out, long out_planes, int* status, void* ws, size_t ws_bytes,
                     int n3, int stages, hipStream_t stream);
 
+/* Baseline JPEG encode of N images of one geometry (csrc/jpeg_encode.hip): images is uint8 (N, H, W) for C = 1 or interleaved
+ * BGR (N, H, W, 3) for C = 3 (written as YCbCr 4:2:0); every file is byte-identical with libjpeg-turbo's default encoder at
+ * that quality (Pillow's Image.save, cv2.imwrite): sequential Huffman, Annex K tables, no restart markers.  quality 1 .. 100,
+ * subsampling 420 (the only one built; 444 / 422 are refused), 1 <= H, W <= 4096, N <= 65535.
+ * egz_jpeg_encode transforms, entropy-codes into the workspace (egz_jpeg_encode_ws_bytes(N, H, W, C) bytes) and writes the
+ * length every file needs to needed[N]; stages: 4 = all of that, 1 / 2 / 3 = stop after the transform / the bit-position
+ * scan / the bit packing (timing; needed is not written).  egz_jpeg_encode_write, given the same workspace and geometry,
+ * writes file i to out[slot_off[i], slot_off[i] + lengths[i]) with lengths[i] the length it needs and status[i] 0 -- or,
+ * where lengths[i] > slot_cap[i] or the slot leaves out's out_bytes, writes nothing of it and sets status[i] 1. */
+size_t egz_jpeg_encode_ws_bytes(int N, int H, int W, int C);
+int egz_jpeg_encode(const unsigned char* images, int N, int H, int W, int C, int quality, int subsampling, void* ws,
+                    size_t ws_bytes, long* needed, int stages, hipStream_t stream);
+int egz_jpeg_encode_write(const void* ws, size_t ws_bytes, int N, int H, int W, int C, unsigned char* out, long out_bytes,
+                          const long* slot_off, const long* slot_cap, long* lengths, int* status, hipStream_t stream);
+
 /* torch.cat((f, g), dim=1) of two one-channel maps, the late-fusion stack's input (models/late_fusion.py:19):
  * f, g [B][1][H][W] -> out [B][2][H][W]; 16-byte copies when HW % 4 == 0 and the pointers are 16-byte aligned, 4-byte ones otherwise. */
 int egz_cat2_planes(const float* f, const float* g, float* out, int B, long HW, hipStream_t stream);
