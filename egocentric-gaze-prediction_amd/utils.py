@@ -258,7 +258,19 @@ def aae_auc_rows(output, target):
 
 
 def aae_auc_from_rows(res, single=False, npix_h=224, npix_w=224):
-    """The host half: the rows of aae_auc_rows (a numpy (B, 6) array) -> computeAAEAUC's return values."""
+    """The host half: the rows of aae_auc_rows (a numpy (B, 6) array) -> computeAAEAUC's return values.
+
+    A prediction whose centre of mass is not a pixel of the map is refused, as the reference refuses it: an all-zero map has a
+    NaN centroid (the reference raises at ``int(nan)``), and negative values can put it outside the image (numpy raises
+    IndexError past the end and silently wraps a negative index; the kernel only compares the centroid, so it can do neither
+    and its count for such a sample means nothing)."""
+    res = np.asarray(res)
+    c = res[:, 4:6]
+    ok = np.isfinite(c).all(1) & (c >= 0).all(1) & (c[:, 0] < npix_h) & (c[:, 1] < npix_w)
+    if not ok.all():
+        b = int(np.flatnonzero(~ok)[0])
+        raise ValueError(f"computeAAEAUC: sample {b} has its centre of mass at ({c[b, 0]}, {c[b, 1]}), not inside the "
+                         f"{npix_h} x {npix_w} map (an all-zero or partly negative prediction)")
     gp = [[int(r[2]), int(r[3])] for r in res]
     if single:
         return float(res[0, 0]), 1 - float(res[0, 1]) / (npix_h * npix_w), gp
