@@ -66,6 +66,11 @@ __global__ void pixel_weighted_sum_kernel(const float* __restrict__ feat, const 
     out[idx] = s;
 }
 
+// torch.min / torch.max PROPAGATE a NaN (fminf / fmaxf drop it): a NaN sum makes the minimum NaN and with it the whole map, as
+// AT.get_weighted's `feature - torch.min(feature)` does
+__device__ __forceinline__ float min_nan(float a, float b) { return (a != a || b != b) ? NAN : fminf(a, b); }
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? NAN : fmaxf(a, b); }
+
 // one block per image: out[p] = sum_c feat[p][c] * w[c]; then (out - min) / max(out - min)
 __global__ __launch_bounds__(256) void weighted_minmax_kernel(const float* __restrict__ feat, const float* __restrict__ w,
                                                                float* __restrict__ out, int HW, int C) {
@@ -82,11 +87,11 @@ __global__ __launch_bounds__(256) void weighted_minmax_kernel(const float* __res
     }
     __syncthreads();
     float mn = INFINITY, mx = -INFINITY;
-    for (int p = tid; p < HW; p += 256) { mn = fminf(mn, vals[p]); mx = fmaxf(mx, vals[p]); }
+    for (int p = tid; p < HW; p += 256) { mn = min_nan(mn, vals[p]); mx = max_nan(mx, vals[p]); }
     red[tid] = mn; red[256 + tid] = mx;
     __syncthreads();
     for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) { red[tid] = fminf(red[tid], red[tid + st]); red[256 + tid] = fmaxf(red[256 + tid], red[256 + tid + st]); }
+        if (tid < st) { red[tid] = min_nan(red[tid], red[tid + st]); red[256 + tid] = max_nan(red[256 + tid], red[256 + tid + st]); }
         __syncthreads();
     }
     mn = red[0];

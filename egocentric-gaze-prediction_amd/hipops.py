@@ -1738,14 +1738,39 @@ def _ptr_table(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
 
 
+def _lstm_b1_dims(params, h0, c0, what):
+    """(L, C, H, N) of a 4L + 2 parameter list in state-dict order.  The C-ABI takes one (C, H, N) and strides every buffer by
+    it, so a tensor of another shape would be read or written out of bounds: ValueError before anything is launched.
+    (The step is launch-bound and runs once per fixation sample: the check is 4L + 4 tuple comparisons, 5 us of host time per
+    call at L = 2, measured with timeit; profiles/b1_glue_tests.txt.)"""
+    n = len(params)
+    if n < 6 or (n - 2) % 4:
+        raise ValueError(f"{what}: {n} parameters, expected 4 L + 2 (w_ih, w_hh, b_ih, b_hh per layer, lin.weight, lin.bias)")
+    L = (n - 2) // 4
+    if params[0].dim() != 2 or params[1].dim() != 2 or params[-2].dim() != 2:
+        raise ValueError(f"{what}: w_ih_l0, w_hh_l0 and lin.weight must be matrices")
+    C, Hd, N = params[0].shape[1], params[1].shape[1], params[-2].shape[0]
+    want = []
+    for l in range(L):
+        want += [(4 * Hd, C if l == 0 else Hd), (4 * Hd, Hd), (4 * Hd,), (4 * Hd,)]
+    want += [(N, Hd), (N,), (L, Hd)]
+    for i, t in enumerate(params):
+        if t.shape != want[i]:
+            raise ValueError(f"{what}: parameter {i} has shape {tuple(t.shape)}, expected {want[i]} (L={L} C={C} H={Hd} N={N})")
+    if h0.shape != want[-1] or c0.shape != want[-1]:
+        raise ValueError(f"{what}: h0 {tuple(h0.shape)} / c0 {tuple(c0.shape)}, expected {(L, Hd)}")
+    return L, C, Hd, N
+
+
 def lstm_b1_fwd(params, inp, h0, c0, want_acts: bool = True):
     """The whole lstmnet step at T = 1, B = 1 in one call (csrc/lstm_b1.hip).  params: state-dict order, 4L + 2 tensors;
     inp (C,) raw; h0, c0 (L,H) -> (xt (C,), acts (L,4H) | None, hn (L,H), cn (L,H), out (N,))."""
-    L = (len(params) - 2) // 4
+    L, C, Hd, N = _lstm_b1_dims(params, h0, c0, "lstm_b1_fwd")
     for i, t in enumerate(params):
         _req(t, f"param{i}")
     _req(inp, "input"); _req(h0, "h0"); _req(c0, "c0")
-    C, Hd, N = params[0].shape[1], params[1].shape[1], params[-2].shape[0]
+    if inp.numel() != C:
+        raise ValueError(f"lstm_b1_fwd: input of {inp.numel()} values, expected C = {C}")
     dev = inp.device
     xt = torch.empty(C, dtype=torch.float32, device=dev)
     acts = torch.empty((L, 4 * Hd), dtype=torch.float32, device=dev) if want_acts else None
@@ -1759,11 +1784,17 @@ def lstm_b1_fwd(params, inp, h0, c0, want_acts: bool = True):
 
 def lstm_b1_bwd(params, grads, dout, dhn, dcn, xt, acts, h0, c0, hn, cn, out):
     """Backward of lstm_b1_fwd: fills the tensors in ``grads`` (same order as params; None entries are skipped)."""
-    L = (len(params) - 2) // 4
-    C, Hd, N = params[0].shape[1], params[1].shape[1], params[-2].shape[0]
+    L, C, Hd, N = _lstm_b1_dims(params, h0, c0, "lstm_b1_bwd")
     for name, t in (("dout", dout), ("dhn", dhn), ("dcn", dcn)):
         if t is not None:
             _req(t, name)
+    if len(grads) != len(params) or any(g is not None and g.numel() != p.numel() for g, p in zip(grads, params)):
+        raise ValueError(f"lstm_b1_bwd: the gradient buffers do not match the {len(params)} parameters")
+    sizes = (("dout", dout, N), ("dhn", dhn, L * Hd), ("dcn", dcn, L * Hd), ("xt", xt, C), ("acts", acts, L * 4 * Hd),
+             ("hn", hn, L * Hd), ("cn", cn, L * Hd), ("out", out, N))
+    for name, t, want in sizes:
+        if t is not None and t.numel() != want:
+            raise ValueError(f"lstm_b1_bwd: {name} holds {t.numel()} values, expected {want} (L={L} C={C} H={Hd} N={N})")
     nbytes = LIB.egz_lstm_b1_ws_bytes(L, C, Hd, N)
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=out.device)
     check(LIB.egz_lstm_b1_bwd(_ptr_table(params), _ptr_table(grads), L, dout.data_ptr(), _p(dhn), _p(dcn), xt.data_ptr(),

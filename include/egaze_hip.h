@@ -452,6 +452,8 @@ int egz_window_mean(const float* feat, const int* win, float* out, int B, int H,
 /* AT.crop_align_feature + mean (AT.py:41-56,229; extractLSTMw.py:32-44, `--align`): the mean of a window of the bilinearly
  * x16-upsampled map is a linear functional of the map -- out[b][c] = sum_p wmap[b][p] * feat[b][p][c] */
 int egz_pixel_weighted_sum(const float* feat, const float* wmap, float* out, int B, int HW, int C, hipStream_t stream);
+/* AT.get_weighted (AT.py:58-66): channel-weighted sum, (x - min) / max(x - min) per map, HW <= 4096.  A NaN sum makes the whole
+ * map NaN, as torch.min / torch.max propagate it */
 int egz_weighted_minmax(const float* feat, const float* w, float* out, int B, int HW, int C, hipStream_t stream);
 
 /* Config-1 glue (run_spatialstream.py:99-104,130-136): centre of mass of the uint8-quantised gaze map exactly as
