@@ -138,6 +138,18 @@ SIGNATURES = {
     "egz_jpeg_encode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "egz_jpeg_encode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, c_int, S]),
     "egz_jpeg_encode_write": (c_int, [P, c_size_t, c_int, c_int, c_int, c_int, P, c_long, P, P, P, P, S]),
+    # --- TV-L1 optical flow (csrc/flow_tvl1.hip)
+    "egz_tvl1_default_k": (c_int, []),
+    "egz_bgr_to_gray_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, S]),
+    "egz_flow_gauss": (c_int, [P, c_int, c_int, c_int, c_int, P, c_int, P, P, S]),
+    "egz_flow_resample": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_float, S]),
+    "egz_flow_grad": (c_int, [P, c_int, c_int, c_int, P, P, S]),
+    "egz_tvl1_warp": (c_int, [P, P, P, P, P, c_int, c_int, c_int, S]),
+    "egz_tvl1_iterate": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double, S]),
+    "egz_flow_to_u8": (c_int, [P, c_long, c_double, P, S]),
+    "egz_tvl1_flow_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_double]),
+    "egz_tvl1_flow": (c_int, [P, c_int, c_int, c_int, P, c_int, P, c_int, c_double, c_double, c_double, c_int, c_double,
+                              c_int, c_int, c_int, P, c_size_t, P, P, S]),
     "egz_adam_step": (c_int, [P, P, P, P, c_long, c_double, c_double, c_double, c_double, c_int, c_double, P, S]),
     "egz_adam_step_dev": (c_int, [P, P, P, P, c_long, c_double, c_double, c_double, c_double, P, c_double, P, S]),
 }

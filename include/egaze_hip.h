@@ -465,6 +465,40 @@ int egz_u8_center_of_mass(const float* map, int B, int H, int W, double* com, in
 int egz_bilinear_up(const float* src, float* dst, int B, int h, int w, int scale, int align_corners, long dst_bstride,
                     hipStream_t stream);
 
+/* Dual TV-L1 optical flow (csrc/flow_tvl1.hip; DESIGN.md "TV-L1 optical flow"; data/extract_flow.py): the flow_x / flow_y images
+ * of the temporal stream from a run of grey frames.  A batch of N pairs is a run of F = N + 1 planes, pair i = planes i, i + 1;
+ * images are 16 .. 2048 pixels per side; a shape or parameter outside its range returns an error and launches nothing.
+ *   egz_bgr_to_gray_u8  BGR bytes, interleaved (N, H, W, 3) or planar (N, 3, H, W), -> (N, H, W) by OpenCV's 8-bit rule
+ *                       (4899 R + 9617 G + 1868 B + 8192) >> 14.
+ *   egz_flow_gauss      separable Gaussian, replicated border, of uint8 (src_u8) or float planes; gw: 2 R + 1 float taps on the
+ *                       device (scipy.ndimage's); tmp, dst: planes x H x W floats each, distinct.
+ *   egz_flow_resample   Keys bicubic (a = -0.5), position and taps clamped: dst(i, j) = scale * src((i + .5) hs / hd - .5, ..).
+ *   egz_flow_grad       central differences, replicated border.
+ *   egz_tvl1_warp       img: N + 1 planes; i1x, i1y: gradient of planes 1 .. N; u: state (u1, u2 read); consts (4, N, H, W)
+ *                       = gx, gy, gx^2 + gy^2, I1w - gx u1 - gy u2 - I0 with I1, its gradient sampled at x + u.
+ *   egz_tvl1_iterate    `iterations` inner iterations on the state (6, N, H, W) = u1 u2 p11 p12 p21 p22 read from a, k per
+ *                       launch: 1 = one streaming launch per iteration, 2 / 3 / 4 / 6 / 8 = overlapped tiles in LDS, 0 =
+ *                       egz_tvl1_default_k(); every k gives the same bits.  The result is in a if ceil(iterations / k) is even,
+ *                       else in b; the other buffer is overwritten.
+ *   egz_flow_to_u8      v > bound -> 255, v < -bound -> 0, else rint(255 (v + bound) / (2 bound)) in double, half to even.
+ *   egz_tvl1_flow       the whole chain on (F, H, W) grey bytes -> u1, u2 (F - 1, H, W) floats; gw0 / gw1: presmoothing /
+ *                       pyramid taps; ws: egz_tvl1_flow_ws_bytes(F, H, W, nscales, zfactor) bytes (0 = arguments out of range). */
+int egz_tvl1_default_k(void);
+int egz_bgr_to_gray_u8(const unsigned char* src, int N, int H, int W, int planar, unsigned char* dst, hipStream_t stream);
+int egz_flow_gauss(const void* src, int src_u8, int planes, int H, int W, const float* gw, int R, float* tmp, float* dst,
+                   hipStream_t stream);
+int egz_flow_resample(const float* src, int planes, int hs, int ws, float* dst, int hd, int wd, float scale, hipStream_t stream);
+int egz_flow_grad(const float* img, int planes, int H, int W, float* gx, float* gy, hipStream_t stream);
+int egz_tvl1_warp(const float* img, const float* i1x, const float* i1y, const float* u, float* consts, int N, int H, int W,
+                  hipStream_t stream);
+int egz_tvl1_iterate(float* a, float* b, const float* consts, int N, int H, int W, int iterations, int k, double tau,
+                     double lambda, double theta, hipStream_t stream);
+int egz_flow_to_u8(const float* v, long n, double bound, unsigned char* out, hipStream_t stream);
+size_t egz_tvl1_flow_ws_bytes(int F, int H, int W, int nscales, double zfactor);
+int egz_tvl1_flow(const unsigned char* frames, int F, int H, int W, const float* gw0, int R0, const float* gw1, int R1,
+                  double tau, double lambda, double theta, int nscales, double zfactor, int warps, int iterations, int k,
+                  void* ws, size_t ws_bytes, float* u1, float* u2, hipStream_t stream);
+
 /* ---- measurement aid (bench.py): sustained v_mfma_f32_32x32x16_f16 rate of this chip on the given operand bits; frag =
  *      16 x 64 x 16 bytes, out = blocks x 256 floats; executes blocks x 4 x iters x 8 MFMAs of 32768 flop. */
 int egz_mfma_probe(const void* frag, float* out, int blocks, int iters, hipStream_t stream);
