@@ -1264,19 +1264,34 @@ int x3p_narrow_blocks(int B, int H, int W) {
     return blocks;
 }
 
+// What a streamed launch is given, whichever kernel form takes it: the host launchers below name only what varies.
+// mask_src is bn_y on the persistent narrow kernel (EPI_BNSUMS); minmax is that kernel's float rows or, on the wide tiles,
+// the zero-filled uint image (mm_out).
+struct ConvArgs {
+    const float* x; const unsigned short* wq; const float* bias; float* y; double* stat;
+    int B, H, W, C, K; float out_scale;
+    const unsigned int* a_absmax; const float* mask_src; unsigned int* absmax_out; const float* bn_coef; float* minmax;
+    hipStream_t st;
+};
+// run-time value -> template argument: a launcher picks the tag and hands it to a generic lambda
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename T> struct TypeTag { using type = T; };
+
 template <typename T>
-int launch_x3p_narrow(int epi, const float* x, const unsigned short* wq, const float* bias, float* y, double* stat, int B, int H,
-                      int W, int C, int K, float out_scale, const unsigned int* a_absmax, const float* bn_y, const float* bn_coef,
-                      float* mm_out, hipStream_t st) {
-    const int total = (int)((long)B * H * W / 256);
-    const int blocks = x3p_narrow_blocks(B, H, W);
-#define EGZ_X3P(E, BN) hipLaunchKernelGGL((conv3x3_x3p_narrow_kernel<T, E, BN>), dim3(blocks), dim3(256), 0, st, x, wq, bias, y, stat, B, H, W, C, K, out_scale, total, a_absmax, bn_y, bn_coef, mm_out)
-    const bool bnin = bn_coef && epi != EPI_BNSUMS;             // forward epilogues: bn_coef = the INPUT's deferred BatchNorm
-    if (epi == EPI_BNSUMS) EGZ_X3P(EPI_BNSUMS, false);
-    else if (epi == EPI_BIAS) { if (bnin) EGZ_X3P(EPI_BIAS, true); else EGZ_X3P(EPI_BIAS, false); }
-    else if (epi == EPI_BIAS_RELU) { if (bnin) EGZ_X3P(EPI_BIAS_RELU, true); else EGZ_X3P(EPI_BIAS_RELU, false); }
-    else { if (bnin) EGZ_X3P(EPI_BIAS_STATS, true); else EGZ_X3P(EPI_BIAS_STATS, false); }
-#undef EGZ_X3P
+int launch_x3p_narrow(int epi, const ConvArgs& a) {
+    const int total = (int)((long)a.B * a.H * a.W / 256);
+    const int blocks = x3p_narrow_blocks(a.B, a.H, a.W);
+    const bool bnin = a.bn_coef && epi != EPI_BNSUMS;           // forward epilogues: bn_coef = the INPUT's deferred BatchNorm
+    auto go = [&](auto e, auto bn) {
+        hipLaunchKernelGGL((conv3x3_x3p_narrow_kernel<T, decltype(e)::value, decltype(bn)::value>), dim3(blocks), dim3(256), 0,
+                           a.st, a.x, a.wq, a.bias, a.y, a.stat, a.B, a.H, a.W, a.C, a.K, a.out_scale, total, a.a_absmax,
+                           a.mask_src, a.bn_coef, a.minmax);
+    };
+    auto fwd = [&](auto e) { if (bnin) go(e, std::true_type{}); else go(e, std::false_type{}); };
+    if (epi == EPI_BNSUMS) go(Int<EPI_BNSUMS>{}, std::false_type{});
+    else if (epi == EPI_BIAS) fwd(Int<EPI_BIAS>{});
+    else if (epi == EPI_BIAS_RELU) fwd(Int<EPI_BIAS_RELU>{});
+    else fwd(Int<EPI_BIAS_STATS>{});
     EGZ_CHECK_LAUNCH("egz_conv3x3_fwd_streamed(narrow)");
     return 0;
 }
@@ -1364,60 +1379,73 @@ int x3s_splits(int B, int H, int W, int C, int K) {
     return ns < 2 ? 1 : (int)ns;
 }
 
-template <typename T>
-int launch_x3s_splitk(int epi, const float* x, const unsigned short* wq, const float* bias, float* y, double* stat, int B, int H,
-                      int W, int C, int K, float out_scale, const unsigned int* a_absmax, float* part, int nsplit,
-                      unsigned int* absmax_out, hipStream_t st) {
-    using G = Geo<1>;
-    const long M = (long)B * H * W;
-    const int Cp = (C + 31) / 32 * 32, Kp = (K + 31) / 32 * 32;
-    const bool patch = (W % 16 == 0) && (H % G::PROWS == 0);
+// Tile grid of a launch over a B x Ho x Wo output image: patch geometry where the image divides into whole patches, raster runs
+// elsewhere; `mult` blocks per tile (the splits of a split-K launch, the four phases of the upsample forward).
+struct TileGrid { bool patch; int mt, total; dim3 grid; };
+template <int WM>
+TileGrid x3s_grid(int B, int Ho, int Wo, int K, int mult) {
+    using G = Geo<WM>;
+    const long M = (long)B * Ho * Wo;
+    const bool patch = (Wo % 16 == 0) && (Ho % G::PROWS == 0);
     const int mt = patch ? (int)(M / G::BM) : egz_cdiv(M, G::BM);
-    const int total = mt * (Kp / G::BN) * nsplit;
-    const dim3 grid(((total + 7) / 8) * 8);
-    if (patch) hipLaunchKernelGGL((conv3x3_igemm_x3s_kernel<T, 1, EPI_PARTIAL, true, PLAIN>), grid, dim3(G::NTHR), 0, st, x, wq, nullptr, part, nullptr, B, H, W, C, K, Cp, Kp, out_scale, mt, total, a_absmax, nullptr, nullptr, nsplit, nullptr);
-    else       hipLaunchKernelGGL((conv3x3_igemm_x3s_kernel<T, 1, EPI_PARTIAL, false, PLAIN>), grid, dim3(G::NTHR), 0, st, x, wq, nullptr, part, nullptr, B, H, W, C, K, Cp, Kp, out_scale, mt, total, a_absmax, nullptr, nullptr, nsplit, nullptr);
+    const int total = mt * ((K + 31) / 32 * 32 / G::BN) * mult;
+    return {patch, mt, total, dim3(((total + 7) / 8) * 8)};
+}
+
+// the one place that spells out the kernel's argument list
+template <typename T, int WM, int EPI, int MODE, bool PRE>
+void x3s_go(const ConvArgs& a, const TileGrid& g, int nsplit) {
+    const int Cp = (a.C + 31) / 32 * 32, Kp = (a.K + 31) / 32 * 32;
+    auto go = [&](auto p) {
+        hipLaunchKernelGGL((conv3x3_igemm_x3s_kernel<T, WM, EPI, decltype(p)::value, MODE, PRE>), g.grid, dim3(Geo<WM>::NTHR), 0,
+                           a.st, a.x, a.wq, a.bias, a.y, a.stat, a.B, a.H, a.W, a.C, a.K, Cp, Kp, a.out_scale, g.mt, g.total,
+                           a.a_absmax, a.mask_src, a.absmax_out, nsplit, reinterpret_cast<unsigned int*>(a.minmax));
+    };
+    if (g.patch) go(std::true_type{}); else go(std::false_type{});
+}
+
+// a: the arguments of the unsplit launch; part: the workspace of nsplit partial results
+template <typename T>
+int launch_x3s_splitk(int epi, const ConvArgs& a, float* part, int nsplit) {
+    ConvArgs pa = a;                   // the partial launch: raw accumulators into the workspace, no epilogue operands
+    pa.bias = nullptr, pa.y = part, pa.stat = nullptr, pa.mask_src = nullptr, pa.absmax_out = nullptr, pa.minmax = nullptr;
+    x3s_go<T, 1, EPI_PARTIAL, PLAIN, false>(pa, x3s_grid<1>(a.B, a.H, a.W, a.K, nsplit), nsplit);
     EGZ_CHECK_LAUNCH("egz_conv3x3_fwd_streamed_splitk");
-    const dim3 fg(egz_cdiv(M, FIX_ROWS), egz_cdiv(K, 64));
-    if (epi == EPI_BIAS) hipLaunchKernelGGL(splitk_fixup_kernel<EPI_BIAS>, fg, dim3(256), 0, st, part, bias, y, stat, M, K, nsplit, nullptr);
-    else if (epi == EPI_BIAS_RELU) hipLaunchKernelGGL(splitk_fixup_kernel<EPI_BIAS_RELU>, fg, dim3(256), 0, st, part, bias, y, stat, M, K, nsplit, absmax_out);
-    else hipLaunchKernelGGL(splitk_fixup_kernel<EPI_BIAS_STATS>, fg, dim3(256), 0, st, part, bias, y, stat, M, K, nsplit, nullptr);
+    const long M = (long)a.B * a.H * a.W;
+    const dim3 fg(egz_cdiv(M, FIX_ROWS), egz_cdiv(a.K, 64));
+    auto fix = [&](auto e, unsigned int* amo) {
+        hipLaunchKernelGGL(splitk_fixup_kernel<decltype(e)::value>, fg, dim3(256), 0, a.st, part, a.bias, a.y, a.stat, M, a.K, nsplit, amo);
+    };
+    if (epi == EPI_BIAS) fix(Int<EPI_BIAS>{}, nullptr);
+    else if (epi == EPI_BIAS_RELU) fix(Int<EPI_BIAS_RELU>{}, a.absmax_out);
+    else fix(Int<EPI_BIAS_STATS>{}, nullptr);
     EGZ_CHECK_LAUNCH("egz_conv3x3_fwd_streamed_splitk(fixup)");
     return 0;
 }
 
 template <typename T, int WM, int MODE>
-int launch_x3s(int epi, const float* x, const unsigned short* wq, const float* bias, float* y, double* stat, int B, int H,
-               int W, int C, int K, float out_scale, const unsigned int* a_absmax, const float* mask_src,
-               unsigned int* absmax_out, hipStream_t st, unsigned int* mm_out = nullptr, bool pre = false) {
-    using G = Geo<WM>;
-    const int Ho = (MODE != PLAIN) ? H / 2 : H, Wo = (MODE != PLAIN) ? W / 2 : W;
-    const long M = (long)B * Ho * Wo;
-    const int Cp = (C + 31) / 32 * 32, Kp = (K + 31) / 32 * 32;
-    const bool patch = (Wo % 16 == 0) && (Ho % G::PROWS == 0);
-    const int mt = patch ? (int)(M / G::BM) : egz_cdiv(M, G::BM);
-    const int total = mt * (Kp / G::BN) * ((MODE == UPSF) ? 4 : 1);
-    dim3 grid(((total + 7) / 8) * 8);
+int launch_x3s(int epi, bool pre, ConvArgs a) {
+    TileGrid g = x3s_grid<WM>(a.B, (MODE != PLAIN) ? a.H / 2 : a.H, (MODE != PLAIN) ? a.W / 2 : a.W, a.K, (MODE == UPSF) ? 4 : 1);
 #ifdef EGZ_TILE_LOOP
     {
         static const int cap = getenv("EGZ_GRID_CAP") ? atoi(getenv("EGZ_GRID_CAP")) / 8 * 8 : 0;
-        if (cap > 0 && (int)grid.x > cap) grid.x = cap;
+        if (cap > 0 && (int)g.grid.x > cap) g.grid.x = cap;
     }
 #endif
-#define EGZ_X3S(E, P) hipLaunchKernelGGL((conv3x3_igemm_x3s_kernel<T, WM, E, P, MODE>), grid, dim3(G::NTHR), 0, st, x, wq, bias, y, stat, B, H, W, C, K, Cp, Kp, out_scale, mt, total, a_absmax, mask_src, absmax_out, 1, mm_out)
-    if (epi != EPI_BIAS_RELU && epi != EPI_MASK_SUMS && epi != EPI_BIAS && epi != EPI_BNSUMS) absmax_out = nullptr;
+    if (epi != EPI_BIAS_RELU && epi != EPI_MASK_SUMS && epi != EPI_BIAS && epi != EPI_BNSUMS) a.absmax_out = nullptr;
+    // (EPI, pre) resolved once; the `if constexpr` guards below decide which of them exist for this (T, WM, MODE)
+    auto go = [&](auto e, auto pr) { x3s_go<T, WM, decltype(e)::value, MODE, decltype(pr)::value>(a, g, 1); };
+    constexpr std::false_type split_here{};              // (PRE = false: the kernel splits the fp32 operand while staging it)
     if (pre) {                         // pre-split activation operand: the training forward of the wide encoder layers
         if constexpr (MODE == PLAIN && (WM == 1 || WM == 2) && IS_F16<T>) {
-#define EGZ_X3P(E, P) hipLaunchKernelGGL((conv3x3_igemm_x3s_kernel<T, WM, E, P, PLAIN, true>), grid, dim3(G::NTHR), 0, st, x, wq, bias, y, stat, B, H, W, C, K, Cp, Kp, out_scale, mt, total, a_absmax, mask_src, absmax_out, 1, mm_out)
             // epi 2: the training forward over pre-split activations; epi 0 / 5: data gradients over a pre-split gradient
-            if (epi == EPI_BIAS_STATS) { if (patch) EGZ_X3P(EPI_BIAS_STATS, true); else EGZ_X3P(EPI_BIAS_STATS, false); }
-            else if (epi == EPI_BIAS)  { if (patch) EGZ_X3P(EPI_BIAS, true); else EGZ_X3P(EPI_BIAS, false); }
-            else if (epi == EPI_BNSUMS) { if (patch) EGZ_X3P(EPI_BNSUMS, true); else EGZ_X3P(EPI_BNSUMS, false); }
+            if (epi == EPI_BIAS_STATS) go(Int<EPI_BIAS_STATS>{}, std::true_type{});
+            else if (epi == EPI_BIAS) go(Int<EPI_BIAS>{}, std::true_type{});
+            else if (epi == EPI_BNSUMS) go(Int<EPI_BNSUMS>{}, std::true_type{});
             else {
                 egz_set_error("egz_conv3x3_fwd_streamed: a pre-split operand is taken by epi 0 / 2 / 5 only");
                 return (int)hipErrorInvalidValue;
             }
-#undef EGZ_X3P
             EGZ_CHECK_LAUNCH("egz_conv3x3_fwd_streamed(pre-split)");
             return 0;
         } else {
@@ -1430,32 +1458,24 @@ int launch_x3s(int epi, const float* x, const unsigned short* wq, const float* b
             egz_set_error("egz_conv3x3_fwd_streamed: the upsample forward has the bias and bias + ReLU epilogues only");
             return (int)hipErrorInvalidValue;
         }
-        if (patch) { if (epi == EPI_BIAS) EGZ_X3S(EPI_BIAS, true); else EGZ_X3S(EPI_BIAS_RELU, true); }
-        else       { if (epi == EPI_BIAS) EGZ_X3S(EPI_BIAS, false); else EGZ_X3S(EPI_BIAS_RELU, false); }
+        if (epi == EPI_BIAS) go(Int<EPI_BIAS>{}, split_here); else go(Int<EPI_BIAS_RELU>{}, split_here);
     } else if (epi == EPI_BNSUMS) {
         if constexpr ((WM == 1 || WM == 2) && MODE == PLAIN) {      // data gradients of the encoders: 128- / 64-column 4-wave tiles
-            if (patch) EGZ_X3S(EPI_BNSUMS, true); else EGZ_X3S(EPI_BNSUMS, false);
+            go(Int<EPI_BNSUMS>{}, split_here);
         } else {
             egz_set_error("egz_conv3x3_fwd_streamed: the BatchNorm-sums epilogue is built for the 128- / 64-column tiles of plain convs");
             return (int)hipErrorInvalidValue;
         }
     } else if (epi == EPI_MASK_SUMS) {
         if constexpr ((WM == 1 || WM == 2) && MODE != UPSF) {      // data gradients of the SP decoder: 128- and 64-column 4-wave tiles
-            if (patch) EGZ_X3S(EPI_MASK_SUMS, true); else EGZ_X3S(EPI_MASK_SUMS, false);
+            go(Int<EPI_MASK_SUMS>{}, split_here);
         } else {
             egz_set_error("egz_conv3x3_fwd_streamed: the mask epilogue is not built for 32-column tiles");
             return (int)hipErrorInvalidValue;
         }
-    } else if (patch) {
-        if (epi == EPI_BIAS) EGZ_X3S(EPI_BIAS, true);
-        else if (epi == EPI_BIAS_RELU) EGZ_X3S(EPI_BIAS_RELU, true);
-        else EGZ_X3S(EPI_BIAS_STATS, true);
-    } else {
-        if (epi == EPI_BIAS) EGZ_X3S(EPI_BIAS, false);
-        else if (epi == EPI_BIAS_RELU) EGZ_X3S(EPI_BIAS_RELU, false);
-        else EGZ_X3S(EPI_BIAS_STATS, false);
-    }
-#undef EGZ_X3S
+    } else if (epi == EPI_BIAS) go(Int<EPI_BIAS>{}, split_here);
+    else if (epi == EPI_BIAS_RELU) go(Int<EPI_BIAS_RELU>{}, split_here);
+    else go(Int<EPI_BIAS_STATS>{}, split_here);
     EGZ_CHECK_LAUNCH("egz_conv3x3_fwd_streamed");
     return 0;
 }
@@ -1571,63 +1591,51 @@ EGZ_API int egz_conv3x3_fwd_streamed(const float* x, const void* wq, const float
                   epi != EPI_MASK_SUMS && (!minmax_out || epi == EPI_BIAS_STATS)),
                   "egz_conv3x3_fwd_streamed: a deferred-BatchNorm input (bn_coef) exists on the narrow persistent kernel only (C, K <= 32, "
                   "H and W multiples of 16); minmax_out needs epi 2 and that geometry or K %% 64 == 0");
-    unsigned int* mmw = wide_mm ? reinterpret_cast<unsigned int*>(minmax_out) : nullptr;
     if (epi == EPI_BNSUMS) {       // data gradient + the BatchNorm-backward sums of the layer below
         EGZ_CHECK_ARG((dtype == 1 || dtype == 2) && mode == 0 && mask_src && bn_coef && stat_partial && !bias &&
                       egz_conv3x3_streamed_ok(B, H, W, C, K, 0) && (x3p_narrow_ok(B, H, W, C, K) || K % 64 == 0),
                       "egz_conv3x3_fwd_streamed: epi 5 (BatchNorm sums) needs mode 0, the narrow geometry (C, K <= 32, H and W "
                       "multiples of 16) or K %% 64 == 0, mask_src = the pre-BN conv output of the layer below, bn_coef, "
                       "stat_partial and no bias");
-        const unsigned short* w16b = static_cast<const unsigned short*>(wq);
-        const float osb = (dtype == 1) ? 1.f / F16_WSCALE : 1.f;
-        if (x3p_narrow_ok(B, H, W, C, K)) {
-            if (dtype == 1 && p2) return launch_x3p_narrow<egz_f16p2>(epi, x, w16b, nullptr, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, bn_coef, nullptr, st);
-            if (dtype == 1) return launch_x3p_narrow<_Float16>(epi, x, w16b, nullptr, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, bn_coef, nullptr, st);
-            return launch_x3p_narrow<__bf16>(epi, x, w16b, nullptr, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, bn_coef, nullptr, st);
-        }
-        // wide tiles: the coefficient rows travel in the kernel's (otherwise unused) bias argument
-        // (absmax_out, optional: max |y| -- the gradient's abs-max bounds the BatchNorm backward of the block below)
-        if (K % 128 == 0) {
-            if (dtype == 1) return p2 ? launch_x3s<egz_f16p2, 1, PLAIN>(epi, x, w16b, bn_coef, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, absmax_out, st, nullptr, pre) : launch_x3s<_Float16, 1, PLAIN>(epi, x, w16b, bn_coef, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, absmax_out, st, nullptr, pre);
-            return launch_x3s<__bf16, 1, PLAIN>(epi, x, w16b, bn_coef, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, absmax_out, st);
-        }
-        if (dtype == 1) return p2 ? launch_x3s<egz_f16p2, 2, PLAIN>(epi, x, w16b, bn_coef, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, absmax_out, st, nullptr, pre) : launch_x3s<_Float16, 2, PLAIN>(epi, x, w16b, bn_coef, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, absmax_out, st, nullptr, pre);
-        return launch_x3s<__bf16, 2, PLAIN>(epi, x, w16b, bn_coef, y, stat_partial, B, H, W, C, K, osb, x_absmax, mask_src, absmax_out, st);
+    } else {
+        EGZ_CHECK_ARG(egz_conv3x3_streamed_ok(B, H, W, C, K, mode), "egz_conv3x3_fwd_streamed: geometry B=%d H=%d W=%d C=%d K=%d "
+                      "mode=%d is not covered (see egz_conv3x3_streamed_ok)", B, H, W, C, K, mode);
+        EGZ_CHECK_ARG((dtype == 1 || dtype == 2) && epi >= 0 && epi <= 3, "egz_conv3x3_fwd_streamed: bad dtype / epilogue");
+        EGZ_CHECK_ARG(epi < EPI_BIAS_STATS || stat_partial, "egz_conv3x3_fwd_streamed: stats / mask epilogue needs stat_partial");
+        EGZ_CHECK_ARG(epi != EPI_MASK_SUMS || (mask_src && absmax_out && !bias), "egz_conv3x3_fwd_streamed: mask epilogue needs "
+                      "mask_src and absmax_out and takes no bias");
+        // forward of [upsample x2 -> conv] (kind-7 packing): f16 x3 only (the forward arithmetic)
+        EGZ_CHECK_ARG(mode != UPSF || dtype == 1, "egz_conv3x3_fwd_streamed: the upsample forward runs in f16 x3 (dtype 1)");
     }
-    EGZ_CHECK_ARG(egz_conv3x3_streamed_ok(B, H, W, C, K, mode), "egz_conv3x3_fwd_streamed: geometry B=%d H=%d W=%d C=%d K=%d "
-                  "mode=%d is not covered (see egz_conv3x3_streamed_ok)", B, H, W, C, K, mode);
-    EGZ_CHECK_ARG((dtype == 1 || dtype == 2) && epi >= 0 && epi <= 3, "egz_conv3x3_fwd_streamed: bad dtype / epilogue");
-    EGZ_CHECK_ARG(epi < EPI_BIAS_STATS || stat_partial, "egz_conv3x3_fwd_streamed: stats / mask epilogue needs stat_partial");
-    EGZ_CHECK_ARG(epi != EPI_MASK_SUMS || (mask_src && absmax_out && !bias), "egz_conv3x3_fwd_streamed: mask epilogue needs "
-                  "mask_src and absmax_out and takes no bias");
-    const unsigned short* w16 = static_cast<const unsigned short*>(wq);
-    const float os = (dtype == 1) ? 1.f / F16_WSCALE : 1.f;
-    if (mode == 2) {     // forward of [upsample x2 -> conv] (kind-7 packing): f16 x3 only (the forward arithmetic)
-        EGZ_CHECK_ARG(dtype == 1, "egz_conv3x3_fwd_streamed: the upsample forward runs in f16 x3 (dtype 1)");
-        if (K % 128 == 0) return launch_x3s<_Float16, 1, UPSF>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st);
-        return launch_x3s<_Float16, 2, UPSF>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st);
-    }
-    if (mode == 1) {
-        if (dtype == 1) return p2 ? launch_x3s<egz_f16p2, 1, UPSD>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st) : launch_x3s<_Float16, 1, UPSD>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st);
-        return launch_x3s<__bf16, 1, UPSD>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st);
-    }
-    if (K % 128 == 0) {
-        if (dtype == 1) return p2 ? launch_x3s<egz_f16p2, 1, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st, mmw, pre) : launch_x3s<_Float16, 1, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st, mmw, pre);
-        return launch_x3s<__bf16, 1, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st, mmw);
-    }
-    if (K % 64 == 0) {
-        if (dtype == 1) return p2 ? launch_x3s<egz_f16p2, 2, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st, mmw, pre) : launch_x3s<_Float16, 2, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st, mmw, pre);
-        return launch_x3s<__bf16, 2, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st, mmw);
-    }
-    EGZ_CHECK_ARG(!(absmax_out && epi == EPI_BIAS_RELU), "egz_conv3x3_fwd_streamed: the abs-max epilogue exists for 64- and "
+    // column tile: 128 (WM 1), 64 (WM 2), else the persistent narrow form or the 32-column tile (WM 4).  `narrow` (K <= 32) is
+    // never true in modes 1 / 2: egz_conv3x3_streamed_ok admits them with K % 64 == 0 only, so they are on the wide tiles.
+    // (minmax_out on the wide tiles is the uint image: the check above admits wide_mm only; pre needs K % 64 == 0 and f16.)
+    const bool narrow = x3p_narrow_ok(B, H, W, C, K) && epi != EPI_MASK_SUMS;
+    const int wm = (K % 128 == 0) ? 1 : (K % 64 == 0) ? 2 : 4;
+    EGZ_CHECK_ARG(wm != 4 || !(absmax_out && epi == EPI_BIAS_RELU), "egz_conv3x3_fwd_streamed: the abs-max epilogue exists for 64- and "
                   "128-column tiles only (K %% 64 == 0)");
-    if (x3p_narrow_ok(B, H, W, C, K) && epi != EPI_MASK_SUMS) {   // persistent narrow form
-        if (dtype == 1 && p2 && epi == EPI_BIAS && !bn_coef) return launch_x3p_narrow<egz_f16p2>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, nullptr, bn_coef, minmax_out, st);
-        if (dtype == 1) return launch_x3p_narrow<_Float16>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, nullptr, bn_coef, minmax_out, st);
-        return launch_x3p_narrow<__bf16>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, nullptr, bn_coef, minmax_out, st);
-    }
-    if (dtype == 1) return p2 ? launch_x3s<egz_f16p2, 4, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st) : launch_x3s<_Float16, 4, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st);
-    return launch_x3s<__bf16, 4, PLAIN>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, mask_src, absmax_out, st);
+    // operand type: the upsample forward is three-product; so is the narrow form but for its epi 5 and plain epi 0 launches
+    const bool two = p2 && mode != UPSF && (!narrow || epi == EPI_BNSUMS || (epi == EPI_BIAS && !bn_coef));
+    ConvArgs a{x, static_cast<const unsigned short*>(wq), bias, y, stat_partial, B, H, W, C, K, (dtype == 1) ? 1.f / F16_WSCALE : 1.f,
+               x_absmax, mask_src, absmax_out, bn_coef, minmax_out, st};
+    // epi 5 on the wide tiles: the coefficient rows travel in the kernel's (otherwise unused) bias argument
+    // (absmax_out, optional: max |y| -- the gradient's abs-max bounds the BatchNorm backward of the block below)
+    if (epi == EPI_BNSUMS && !narrow) a.bias = bn_coef;
+    auto typed = [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (narrow) return launch_x3p_narrow<T>(epi, a);
+        auto tiled = [&](auto w) {
+            auto moded = [&](auto m) {      // built: every plain form; mode 1 on the 128-column tile; mode 2 in f16 x3, 4-wave tiles
+                constexpr int WM = decltype(w)::value, MODE = decltype(m)::value;
+                if constexpr (MODE == PLAIN || (MODE == UPSD && WM == 1) || (MODE == UPSF && WM != 4 && std::is_same<T, _Float16>::value))
+                    return launch_x3s<T, WM, MODE>(epi, pre, a);
+                return (int)hipErrorInvalidValue;      // (not reached: egz_conv3x3_streamed_ok and the checks above admit nothing else)
+            };
+            return mode == PLAIN ? moded(Int<PLAIN>{}) : mode == UPSD ? moded(Int<UPSD>{}) : moded(Int<UPSF>{});
+        };
+        return wm == 1 ? tiled(Int<1>{}) : wm == 2 ? tiled(Int<2>{}) : tiled(Int<4>{});
+    };
+    return dtype == 2 ? typed(TypeTag<__bf16>{}) : two ? typed(TypeTag<egz_f16p2>{}) : typed(TypeTag<_Float16>{});
 }
 
 // Split-K form of a PLAIN launch for small pixel counts (batch-1 inference, the 14 x 14 / 28 x 28 layers at small batches):
@@ -1655,9 +1663,8 @@ EGZ_API int egz_conv3x3_fwd_streamed_splitk(const float* x, const void* wq, cons
     EGZ_CHECK_ARG(nsplit >= 2 && nsplit <= C / 32, "egz_conv3x3_fwd_streamed_splitk: nsplit=%d outside [2, C/32]", nsplit);
     EGZ_CHECK_ARG(ws_bytes >= egz_conv3x3_fwd_streamed_splitk_ws_bytes(B, H, W, K, nsplit),
                   "egz_conv3x3_fwd_streamed_splitk: workspace too small");
-    const unsigned short* w16 = static_cast<const unsigned short*>(wq);
-    const float os = (dtype == 1) ? 1.f / F16_WSCALE : 1.f;
+    const ConvArgs a{x, static_cast<const unsigned short*>(wq), bias, y, stat_partial, B, H, W, C, K, (dtype == 1) ? 1.f / F16_WSCALE : 1.f,
+                     x_absmax, nullptr, absmax_out, nullptr, nullptr, st};
     float* part = static_cast<float*>(workspace);
-    if (dtype == 1) return launch_x3s_splitk<_Float16>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, part, nsplit, absmax_out, st);
-    return launch_x3s_splitk<__bf16>(epi, x, w16, bias, y, stat_partial, B, H, W, C, K, os, x_absmax, part, nsplit, absmax_out, st);
+    return dtype == 1 ? launch_x3s_splitk<_Float16>(epi, a, part, nsplit) : launch_x3s_splitk<__bf16>(epi, a, part, nsplit);
 }

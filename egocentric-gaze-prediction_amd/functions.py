@@ -486,7 +486,7 @@ class HeadSigmoid(torch.autograd.Function):
         xin, out, weight, bias = ctx.saved_tensors
         ng = ctx.needs_input_grad
         sw, sb = H.grad_sink(weight, ng[1]), H.grad_sink(bias, ng[2] and bias is not None)
-        if ctx.relu_below and ng[0] and H.MASK_FUSE and H.HEAD_MASK_FUSE:
+        if ctx.relu_below and ng[0] and H.MASK_FUSE:
             dx, dw, db, stat, am = H.conv1x1_sigmoid_bwd_masked(xin, weight.detach(), out, dout.contiguous(), out_dw=sw,
                                                                 out_db=sb)
             d = from_nhwc(dx)

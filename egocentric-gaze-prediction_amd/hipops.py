@@ -207,7 +207,7 @@ def conv_dtype(role: str, gemm_out: int, gemm_in: int, operand: Optional[torch.T
     if gemm_out % 64 != 0 or gemm_in % 32 != 0:
         # narrow layers (the late-fusion stack: 32 -> 32 -> 8 channels): only the streamed-weight kernel's 32-column tile
         # takes them, and only for plain convs over an operand whose geometry it covers
-        if not (STREAMED and operand is not None and operand.dim() == 4
+        if not (operand is not None and operand.dim() == 4
                 and LIB.egz_conv3x3_streamed_ok(operand.shape[0], operand.shape[1], operand.shape[2], gemm_in, gemm_out, 0)):
             return F32
     return F16X3 if (role == "fwd" or GRAD_SPLIT == "f16") else BF16X3
@@ -216,8 +216,6 @@ def conv_dtype(role: str, gemm_out: int, gemm_in: int, operand: Optional[torch.T
 # Module-level switches of this file are plain constants unless they read the environment: the tests flip them with
 # monkeypatch (each one names the test that exercises its off position); round 4 removed the environment knobs of everything
 # that was measured and decided.
-STREAMED = True           # plain convs on the streamed-weight halo kernel (False: the round-1 LDS-DMA halo / gather kernels)
-UPSF_STREAMED = True      # forward of the four upsample-fused decoder convs on the streamed kernel (MODE UPSF)
 # Split-K form of the streamed kernel when a launch has too few pixel tiles to fill the chip (egz_conv3x3_streamed_splits):
 # batch-1 inference runs its 28 x 28 / 14 x 14 layers on 8-28 of 512 block slots otherwise.  (tests flip the constant)
 # (tests: test_conv3x3_streamed_splitk, the whole-model gradient tests pin the summation order with it).
@@ -229,10 +227,10 @@ def conv_weight(w: torch.Tensor, role: str, dtype: int, x: torch.Tensor, gemm_ou
     Split-half launches whose geometry the streamed-weight kernel covers (egz_conv3x3_streamed_ok) use the MFMA-fragment-
     ordered packing; everything else the plane-ordered one.  role: 'fwd' | 'dgrad' | 'ups_dgrad' (x = the hi-res dy) |
     'ups_fwd' (x = the low-res input of [upsample x2 -> conv]; four phase convolutions, f16 x3 only)."""
-    if dtype and STREAMED:
+    if dtype:
         B, H, W, C = x.shape
         if role == "ups_fwd":
-            if UPSF_STREAMED and dtype == F16X3 and LIB.egz_conv3x3_streamed_ok(B, 2 * H, 2 * W, C, gemm_out, 2):
+            if dtype == F16X3 and LIB.egz_conv3x3_streamed_ok(B, 2 * H, 2 * W, C, gemm_out, 2):
                 return packed_weight(w, "ups_fwd_frag", dtype), True
         elif LIB.egz_conv3x3_streamed_ok(B, H, W, C, gemm_out, 1 if role == "ups_dgrad" else 0):
             return packed_weight(w, role + "_frag", dtype), True
@@ -596,7 +594,7 @@ def presplit_ok(B: int, H: int, W: int, C: int, K_next: int) -> bool:
     """Can the (B, H, W, C) output of a train-mode [BN -> ReLU (-> pool)] block be stored pre-split for a consuming 3x3 conv
     with K_next filters?  Needs the f16 x3 policy with forward scaling, the streamed kernel's 64- / 128-column tiles without
     split-K for the consumer's forward and the split-half 9-tap kernel for its weight gradient."""
-    if not (PRESPLIT and PRECISION == "split" and GRAD_SPLIT == "f16" and FWD_SCALE and STREAMED):
+    if not (PRESPLIT and PRECISION == "split" and GRAD_SPLIT == "f16" and FWD_SCALE):
         return False
     if C % 64 != 0 or K_next % 64 != 0 or C > 512 or 4 * B * H * W * C >= _SPLIT_MAX_BYTES:
         return False
@@ -622,7 +620,7 @@ def presplit_grad_ok(B: int, H: int, W: int, C: int, K: int) -> bool:
     """Can the gradient w.r.t. the (B, H, W, K) output of a C -> K conv (written by that block's BatchNorm backward) be stored
     pre-split?  Its consumers: the conv's data gradient (reduction over K, C output columns, unsplit streamed launch on the
     64- / 128-column tiles) and its weight gradient (the split-half 9-tap kernel)."""
-    if not (PRESPLIT_GRAD and PRESPLIT and PRECISION == "split" and GRAD_SPLIT == "f16" and FWD_SCALE and STREAMED):
+    if not (PRESPLIT_GRAD and PRESPLIT and PRECISION == "split" and GRAD_SPLIT == "f16" and FWD_SCALE):
         return False
     if C % 64 != 0 or K % 64 != 0 or K > 512 or 4 * B * H * W * K >= _SPLIT_MAX_BYTES:
         return False
@@ -636,6 +634,16 @@ def presplit_grad_ok(B: int, H: int, W: int, C: int, K: int) -> bool:
 # FLOP accounting of a launch over a zero-PADDED operand (the 20-channel flow stack runs as 32 channels): the algorithmic count
 # prices the real channels (the padded count over-stated the step's FLOPs by 0.3 %).  Set around the launch.
 ALGO_CHANNELS = [None]
+
+
+def _conv3x3_streamed(label: str, x, wq, y, B: int, H: int, W: int, C: int, K: int, *, bias=None, stat=None, epi: int = 0,
+                      dtype: int, mode: int = 0, pre: bool = False, absmax=None, mask=None, absmax_out=None, bn=None,
+                      minmax=None) -> None:
+    """One launch of egz_conv3x3_fwd_streamed (GEMM view: x (B, H, W, C) gathered, K columns; mode 0 plain, 1 upsample data
+    gradient, 2 upsample forward; ``pre``: x holds pre-split pairs).  ``label``: the family name check() reports."""
+    check(LIB.egz_conv3x3_fwd_streamed(x.data_ptr(), wq.data_ptr(), _p(bias), y.data_ptr(), _p(stat), B, H, W, C, K, epi, dtype,
+                                       mode | (0x100 if pre else 0), _p(absmax), _p(mask), _p(absmax_out), _p(bn), _p(minmax),
+                                       _stream()), label)
 
 
 def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor], K: int, ups=False,
@@ -681,9 +689,8 @@ def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor],
         if ups == "fold" or epi not in (EPI_BIAS, EPI_BIAS_RELU) or bn_in is not None:
             raise RuntimeError("the streamed upsample forward is the phase form with a bias / bias + ReLU epilogue")
         PROF.note_flops("egz_conv3x3_fwd_split", 2.0 * B * H * W * K * 9 * C)
-        check(LIB.egz_conv3x3_fwd_streamed(x.data_ptr(), wp.data_ptr(), _p(bias), y.data_ptr(), None, B, H, W, C, K,
-                                           epi, dtype, 2, _p(absmax), None, _p(amo), None, None, _stream()),
-              "egz_conv3x3_fwd_split")
+        _conv3x3_streamed("egz_conv3x3_fwd_split", x, wp, y, B, H, W, C, K, bias=bias, epi=epi, dtype=dtype, mode=2,
+                          absmax=absmax, absmax_out=amo)
         return y, None
     if dtype and streamed:       # wp = fragment-ordered packing (conv_weight): weights L2 -> registers, halo through LDS
         PROF.note_flops("egz_conv3x3_fwd_split", 2.0 * B * H * W * K * 9 * (ALGO_CHANNELS[0] or C))
@@ -717,9 +724,8 @@ def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor],
             y._egz_absmax = amo
         if p2:
             _note_p2(dtype, 2.0 * B * H * W * K * 9 * C)
-        check(LIB.egz_conv3x3_fwd_streamed(x.data_ptr(), wp.data_ptr(), _p(bias), y.data_ptr(), _p(stat), B, H, W, C, K,
-                                           epi, _p2(dtype) if p2 else dtype, 0x100 if pre_in else 0, _p(absmax), None, _p(amo), _p(bn_in), _p(mm),
-                                           _stream()), "egz_conv3x3_fwd_split")
+        _conv3x3_streamed("egz_conv3x3_fwd_split", x, wp, y, B, H, W, C, K, bias=bias, stat=stat, epi=epi,
+                          dtype=_p2(dtype) if p2 else dtype, pre=pre_in, absmax=absmax, absmax_out=amo, bn=bn_in, minmax=mm)
         return y, stat
     if pre_in:
         raise RuntimeError("a pre-split activation reached a launch that is not on the streamed kernel")
@@ -759,9 +765,8 @@ def conv3x3_ups_dgrad(dy: torch.Tensor, wp_ups_dgrad: torch.Tensor, C: int, dtyp
         PROF.note_flops("egz_conv3x3_fwd_split", 2.0 * B * H * W * K * 9 * C)
         am = absmax_of(dy) if dtype == F16X3 else None
         _note_p2(dtype, 2.0 * B * H * W * K * 9 * C)
-        check(LIB.egz_conv3x3_fwd_streamed(dy.data_ptr(), wp_ups_dgrad.data_ptr(), None, dx.data_ptr(), None, B, H, W, K, C,
-                                           0, _p2(dtype), 1, _p(am), None, None, None, None, _stream()),
-              "egz_conv3x3_fwd_streamed(ups_dgrad)")
+        _conv3x3_streamed("egz_conv3x3_fwd_streamed(ups_dgrad)", dy, wp_ups_dgrad, dx, B, H, W, K, C, dtype=_p2(dtype), mode=1,
+                          absmax=am)
         return dx
     if dtype:      # GEMM roles: reduction over the conv's K, output channels = the conv's C
         PROF.note_flops("egz_conv3x3_fwd_split", 2.0 * B * H * W * K * 9 * C)
@@ -784,7 +789,6 @@ EPI_MASK_SUMS = 3
 # load.  With the branch-free epilogue (buffer loads / stores with out-of-range offsets for invalid rows, round 3) the step
 # is 0.55 ms faster with it (32.6 vs 33.15 ms, profiles/r03_ab_notes.txt), so it is the default (off position: test_relu_backward_folded_into_dgrad_epilogue flips MASK_FUSE).
 MASK_FUSE = True
-HEAD_MASK_FUSE = True   # the same for the block under the 1x1 head (test_head_sigmoid_masked_backward covers the kernel)
 MASK_FUSE_STATS = {"produced": 0, "consumed": 0}                 # how often the fused form ran / was picked up (tests)
 
 
@@ -806,9 +810,8 @@ def conv3x3_dgrad_masked(dy: torch.Tensor, wq: torch.Tensor, C: int, dtype: int,
     PROF.note_flops("egz_conv3x3_fwd_split", 2.0 * B * H * W * K * 9 * C)
     am = absmax_of(dy) if dtype == F16X3 else None
     _note_p2(dtype, 2.0 * B * H * W * K * 9 * C)
-    check(LIB.egz_conv3x3_fwd_streamed(dy.data_ptr(), wq.data_ptr(), None, dx.data_ptr(), stat.data_ptr(), B, H, W, K, C,
-                                       EPI_MASK_SUMS, _p2(dtype), 1 if ups else 0, _p(am), mask_src.data_ptr(), amo.data_ptr(),
-                                       None, None, _stream()), "egz_conv3x3_fwd_streamed(masked dgrad)")
+    _conv3x3_streamed("egz_conv3x3_fwd_streamed(masked dgrad)", dy, wq, dx, B, H, W, K, C, stat=stat, epi=EPI_MASK_SUMS,
+                      dtype=_p2(dtype), mode=1 if ups else 0, absmax=am, mask=mask_src, absmax_out=amo)
     return dx, stat, amo
 
 
@@ -833,7 +836,7 @@ def bnsums_ok(B: int, H: int, W: int, C: int, K: int, dtype: int) -> bool:
         return False
     if C <= 32 and K <= 32:
         return C % 4 == 0 and K % 4 == 0 and H % 16 == 0 and W % 16 == 0
-    return bool(BNSUMS_WIDE and STREAMED and C % 64 == 0 and K % 32 == 0
+    return bool(BNSUMS_WIDE and C % 64 == 0 and K % 32 == 0
                 and (not SPLITK or LIB.egz_conv3x3_streamed_splits(B, H, W, K, C) <= 1))      # (few-tile launches stay split-K)
 
 
@@ -862,9 +865,8 @@ def conv3x3_dgrad_bnsums(dy: torch.Tensor, wq: torch.Tensor, C: int, dtype: int,
         PRESPLIT_STATS["dgrad"] += 1
     if C % 64 == 0:        # (the narrow late-fusion form of this launch stays three-product)
         _note_p2(dtype, 2.0 * B * H * W * K * 9 * C)
-    check(LIB.egz_conv3x3_fwd_streamed(dy.data_ptr(), wq.data_ptr(), None, dx.data_ptr(), stat.data_ptr(), B, H, W, K, C,
-                                       EPI_BNSUMS, _p2(dtype), 0x100 if pre_in else 0, _p(am), bn_y.data_ptr(), _p(amo), coef.data_ptr(),
-                                       None, _stream()), "egz_conv3x3_fwd_streamed(dgrad + BN sums)")
+    _conv3x3_streamed("egz_conv3x3_fwd_streamed(dgrad + BN sums)", dy, wq, dx, B, H, W, K, C, stat=stat, epi=EPI_BNSUMS,
+                      dtype=_p2(dtype), pre=pre_in, absmax=am, mask=bn_y, absmax_out=amo, bn=coef)
     return dx, stat
 
 
@@ -1002,7 +1004,7 @@ def bn_defer_ok(B: int, H: int, W: int, K: int, K_next: int, first_direct: bool)
     """Can the [BN -> ReLU] of a block with K output channels at (B, H, W) be left to a next 3x3 conv with K_next filters?
     Needs the split-half policy, the persistent narrow conv kernel and the narrow weight-gradient kernel for K -> K_next, and
     a producer that emits per-channel max / min rows (the narrow conv kernel itself, or the direct first-layer kernel)."""
-    if not (BN_DEFER and BNSUMS_FUSE and PRECISION == "split" and GRAD_SPLIT == "f16" and FWD_SCALE and STREAMED):
+    if not (BN_DEFER and BNSUMS_FUSE and PRECISION == "split" and GRAD_SPLIT == "f16" and FWD_SCALE):
         return False
     if not (K in (16, 32) and K_next <= 32 and K_next % 4 == 0 and H % 16 == 0 and W % 16 == 0):
         return False
@@ -1170,11 +1172,9 @@ def bn_relu_pool_bwd(y: torch.Tensor, dout: torch.Tensor, coef: torch.Tensor, po
     return dy, dg, db
 
 
-FIRST_FUSE = True        # first block of a narrow stack: BatchNorm backward + weight gradient in one pass
-
-
 def bn_bwd_first_wgrad_ok(C: int, K: int, pool: bool) -> bool:
-    return bool(FIRST_FUSE and K in (32, 64) and 1 <= C <= 3 and not pool)
+    """First block of a narrow stack: BatchNorm backward + weight gradient in one pass."""
+    return bool(K in (32, 64) and 1 <= C <= 3 and not pool)
 
 
 def bn_bwd_first_wgrad(y: torch.Tensor, dout: torch.Tensor, coef: torch.Tensor, x_nchw: torch.Tensor,

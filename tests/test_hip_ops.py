@@ -1207,3 +1207,138 @@ def test_backward_two_products(B, Hh, Ww, C, K, ups, monkeypatch):
             l2 = float((a.double() - ref).norm() / ref.norm())
             assert rel(a, ref) < tol_max and l2 < tol_l2, (products, name, rel(a, ref), l2)
     assert not torch.equal(got[2][1], got[3][1]) and not torch.equal(got[2][2], got[3][2])
+
+
+# ----------------------------------------------------------------------------- streamed kernel: every leg of the launch dispatch
+_TYPES = {"f16": (1, 2e-6), "f16p2": (0x11, 2e-3), "bf16": (2, 3e-5)}      # dtype code, tolerance: those of the tests above
+_GEO = {"t128p": (32, 128, 16, 16), "t128r": (32, 128, 10, 12), "t64p": (32, 64, 16, 16), "t64r": (32, 64, 10, 12),
+        "t32": (32, 8, 10, 12), "narrow": (32, 32, 16, 16)}               # C, K, H, W: column tile x patch / raster geometry
+DISPATCH_LEGS = (
+    # operand types x tile widths (mode 0, epi 0)
+    [(f"{g}-{t}", g, t, 0, 0, False) for g in _GEO for t in _TYPES]
+    # epilogues 1 / 2 on every tile width, 3 / 5 where they are built (3: the wide tiles; 5: the wide tiles and the narrow form)
+    + [(f"{g}-epi{e}", g, "f16", e, 0, False) for g, e in (
+        ("t128p", 1), ("t64r", 1), ("t32", 1), ("narrow", 1), ("t128r", 2), ("t64p", 2), ("t32", 2), ("narrow", 2),
+        ("t128p", 3), ("t64r", 3), ("t128r", 5), ("t64p", 5), ("narrow", 5))]
+    # the narrow form is two-product for epi 5 and plain epi 0 only: with the bit set, epi 1 must stay at the f16 x3 tolerance
+    + [("narrow-epi5-f16p2", "narrow", "f16p2", 5, 0, False), ("narrow-epi1-p2bit", "narrow", "f16p2", 1, 0, False)]
+    # pre-split operand (C = 64: pairs written by bn_relu_pool_fwd's pre-split form) on the wide tiles
+    + [(f"{g}-pre-epi{e}", g, "f16", e, 0, True) for g in ("t128p", "t64p") for e in (0, 2, 5)]
+    # mode 1: upsample data gradient, 32 x 32 hi-res gradient, 128 GEMM columns; mode 2: upsample forward, 32 x 32 hi-res output
+    + [(f"upsd-{t}", "t128p", t, 0, 1, False) for t in _TYPES] + [("upsd-epi3", "t128p", "f16", 3, 1, False)]
+    + [(f"upsf-{g}-epi{e}", g, "f16", e, 2, False) for g in ("t128p", "t64p") for e in (0, 1)])
+_LEG_CACHE = {}
+
+
+def _leg_operands(g, mode, pre):
+    """Seeded operands of a dispatch leg and its fp64 reference without bias (computed once per geometry, never modified)."""
+    key = (g, mode, pre)
+    if key not in _LEG_CACHE:
+        h = H()
+        C, K, Hh, Ww = _GEO[g]
+        if pre:
+            C = 64
+        w = rnd(K, C, 3, 3, seed=402, scale=(2.0 / (9 * C)) ** 0.5)
+        if mode == 1:       # x = the hi-res gradient of a C <- K conv over an upsampled image: columns = the conv's input channels
+            x = rnd(2, C, 2 * Hh, 2 * Ww, seed=401)
+            wt = rnd(C, K, 3, 3, seed=402, scale=(2.0 / (9 * C)) ** 0.5)
+            lo = torch.zeros(2, K, Hh, Ww, dtype=torch.float64, requires_grad=True)
+            F.conv2d(F.interpolate(lo, scale_factor=2, mode="nearest"), wt.double(), None, padding=1).backward(x.double())
+            ref, kind, xd, wdev = lo.grad, "ups_dgrad_frag", nhwc(x), wt.to(DEV)
+        elif mode == 2:
+            x = rnd(2, C, Hh, Ww, seed=401)
+            ref = F.conv2d(F.interpolate(x.double(), scale_factor=2, mode="nearest"), w.double(), None, padding=1)
+            kind, xd, wdev = "ups_fwd_frag", nhwc(x), w.to(DEV)
+        elif pre:           # producer chain of test_presplit_activation_chain: conv -> bound -> [BN -> ReLU] written as pairs
+            x0, w0 = nhwc(rnd(2, 64, Hh, Ww, seed=403)), rnd(C, 64, 3, 3, seed=404, scale=(2.0 / (9 * 64)) ** 0.5).to(DEV)
+            y0, st0 = h.conv3x3_fwd(x0, h.conv_weight(w0, "fwd", h.F16X3, x0, C)[0], rnd(C, seed=413, scale=0.1).to(DEV), C, epi=h.EPI_BIAS_STATS,
+                                    dtype=h.F16X3, streamed=True, want_bound=True)
+            coef, am = h.bn_finalize(st0, float(2 * Hh * Ww), (1.0 + 0.3 * rnd(C, seed=405)).to(DEV), (0.2 * rnd(C, seed=406)).to(DEV),
+                                     None, None, 0.1, 1e-5, mm=y0._egz_mm)
+            xd = h.bn_relu_pool_fwd(y0, coef, False, presplit_am=am)
+            xd._egz_absmax = am
+            assert xd._egz_presplit
+            ref = F.conv2d(nchw(h.bn_relu_pool_fwd(y0, coef, False)).double(), w.double(), None, padding=1)
+            kind, wdev = "fwd_frag", w.to(DEV)
+        else:
+            x = rnd(2, C, Hh, Ww, seed=401)
+            ref = F.conv2d(x.double(), w.double(), None, padding=1)
+            kind, xd, wdev = "fwd_frag", nhwc(x), w.to(DEV)
+        _LEG_CACHE[key] = (xd, wdev, kind, ref, C, K)
+    return _LEG_CACHE[key]
+
+
+def run_dispatch_leg(h, leg):
+    """One launch of egz_conv3x3_fwd_streamed through hipops._conv3x3_streamed -> dict of what it wrote + the fp64 reference."""
+    _, g, t, epi, mode, pre = leg
+    xd, wdev, kind, ref, C, K = _leg_operands(g, mode, pre)
+    dtype = _TYPES[t][0]
+    B, Hi, Wi = xd.shape[0], xd.shape[1] * (2 if mode == 2 else 1), xd.shape[2] * (2 if mode == 2 else 1)
+    Ho, Wo = (Hi // 2, Wi // 2) if mode == 1 else (Hi, Wi)
+    wq = h.packed_weight(wdev, kind, dtype & 0xf)
+    y = torch.empty((B, Ho, Wo, K), dtype=torch.float32, device=DEV)
+    bias = rnd(K, seed=407, scale=0.1) if epi in (0, 1, 2) else None
+    kw, out = {}, {"y": y}
+    if epi in (2, 3, 5):
+        rows = h.LIB.egz_conv3x3_streamed_stat_rows(B, Ho, Wo, C, K) if mode == 0 else (B * Ho * Wo + 127) // 128
+        kw["stat"] = out["stat"] = torch.empty((rows, 2, K), dtype=torch.float64, device=DEV)
+    if epi in (3, 5):
+        kw["mask"] = out["mask"] = nhwc(rnd(B, K, Ho, Wo, seed=408))
+    if epi == 5:
+        kw["bn"] = out["coef"] = torch.stack([0.1 * rnd(K, seed=409), 1.0 + 0.2 * rnd(K, seed=410).abs(),
+                                              1.0 + 0.3 * rnd(K, seed=411), 0.3 * rnd(K, seed=412)]).contiguous().to(DEV)
+    if epi == 3 or (epi == 1 and K % 64 == 0):
+        kw["absmax_out"] = out["absmax"] = h._new_absmax(DEV)
+    h._conv3x3_streamed("egz_conv3x3_fwd_split", xd, wq, y, B, Hi, Wi, C, K, bias=None if bias is None else bias.to(DEV), epi=epi,
+                        dtype=dtype, mode=mode, pre=pre, absmax=h.absmax_of(xd) if dtype & 0xf == 1 else None, **kw)
+    want = ref if bias is None else ref + bias.double().view(1, -1, 1, 1)
+    if epi == 1:
+        want = F.relu(want)
+    if epi == 3:
+        want = torch.where(nchw(out["mask"]) > 0, want, torch.zeros_like(want))
+    out["want"] = want
+    return out
+
+
+@pytest.mark.parametrize("leg", DISPATCH_LEGS, ids=[l[0] for l in DISPATCH_LEGS])
+def test_streamed_dispatch_legs(leg, monkeypatch):
+    """Every leg of egz_conv3x3_fwd_streamed's launch dispatch once, at the smallest shape that reaches it (B = 2): operand type
+    x tile width (128 / 64 / 32 columns, persistent narrow form) x patch / raster geometry, the epilogues each tile is built
+    with, the pre-split operand, the two upsample modes -- against fp64 conv2d at the tolerances of the tests above (f16 x3
+    2e-6, bf16 x3 3e-5, two products 2e-3; BN statistics 1e-5; BatchNorm-backward sums 2e-6 / 2e-5 as
+    test_dgrad_with_bn_sums_wide).  Larger and ragged shapes of the same legs: test_conv3x3_streamed, _ups_dgrad, _ups_fwd."""
+    h = H()
+    monkeypatch.setattr(h, "SPLITK", False)
+    name, g, t, epi, mode, pre = leg
+    tol = 2e-6 if name == "narrow-epi1-p2bit" else _TYPES[t][1]
+    out = run_dispatch_leg(h, leg)
+    y, want = out["y"], out["want"]
+    err = rel(nchw(y), want)
+    print(name, "rel err", err)
+    assert err < tol
+    if epi == 2:
+        s = out["stat"].sum(0).cpu()
+        assert rel(s[0], want.sum(dim=(0, 2, 3))) < 1e-5 and rel(s[1], (want * want).sum(dim=(0, 2, 3))) < 1e-5
+    if epi == 3:
+        s = out["stat"].sum(0).cpu()
+        assert rel(s[0], want.sum(dim=(0, 2, 3))) < 1e-5                 # plane 0: the bias gradient of the layer below
+    if epi == 5:
+        d64, y64, c64 = y.double(), out["mask"].double(), out["coef"].double()
+        dz = torch.where(y64 * c64[2] + c64[3] > 0, d64, torch.zeros_like(d64))
+        s = out["stat"].sum(0)
+        assert rel(s[0], dz.sum((0, 1, 2))) < 2e-6 and rel(s[1], (dz * (y64 - c64[0]) * c64[1]).sum((0, 1, 2))) < 2e-5
+    if "absmax" in out:
+        assert h.absmax_value(out["absmax"]).item() == y.abs().max().item()
+
+
+def test_streamed_dispatch_splitk_leg(monkeypatch):
+    """... and the split-K leg (SPLITK on, few pixel tiles: C = K = 128, 14 x 14, B = 1), which has its own entry point."""
+    h = H()
+    monkeypatch.setattr(h, "SPLITK", True)
+    x, w, b = rnd(1, 128, 14, 14, seed=421), rnd(128, 128, 3, 3, seed=422, scale=(2.0 / (9 * 128)) ** 0.5), rnd(128, seed=423, scale=0.1)
+    assert h.LIB.egz_conv3x3_streamed_splits(1, 14, 14, 128, 128) >= 2
+    xd, wd = nhwc(x), w.to(DEV)
+    wp, st = h.conv_weight(wd, "fwd", h.F16X3, xd, 128)
+    assert st
+    y, _ = h.conv3x3_fwd(xd, wp, b.to(DEV), 128, epi=h.EPI_BIAS_RELU, dtype=h.F16X3, streamed=True)
+    assert rel(nchw(y), F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1))) < 2e-6

@@ -79,7 +79,7 @@ def main():
         flops = 2.0 * B * Hh * Hh * K * 9 * C
         fdt = a.dtype if (a.dtype and K % 64 == 0) else 0
         ddt = a.dtype if (a.dtype and C % 64 == 0) else 0
-        # plain convs: the packing / kernel hipops picks for this geometry (streamed-weight kernel unless EGAZE_STREAMED=0)
+        # plain convs: the packing / kernel hipops picks for this geometry (the streamed-weight kernel where it covers it)
         wp, fst = H.conv_weight(w, "ups_fwd" if ups else "fwd", fdt, x, K)
         wd, dst = H.conv_weight(w, "dgrad", ddt, dy, C)
         res = []
