@@ -10,6 +10,7 @@
 //   order (lane -> consecutive channel) so every ds_read_b32 is conflict-free without padding.
 #include "egz_common.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -1479,17 +1480,21 @@ __global__ __launch_bounds__(256) void wgrad_reduce_tile_kernel(const float* __r
 }
 // workspace layout: [S][n] partial tiles, then [ceil(S/RG)][n] folded partials when S > RG
 size_t wgrad_ws_floats(int S, long n) { return (size_t)S * n + (S > RG ? (size_t)((S + RG - 1) / RG) * n : 0); }
+// S > RG partials of n floats: folded RG at a time into the rows behind them.  src / rows: what the final pass sums.
+int wgrad_fold(float* part, long n, int S, hipStream_t st, const float*& src, int& rows) {
+    src = part, rows = S;
+    if (S <= RG) return 0;
+    float* part2 = part + (size_t)S * n;
+    rows = (S + RG - 1) / RG;
+    hipLaunchKernelGGL(wgrad_fold_kernel, dim3(egz_cdiv(n, 256), rows), dim3(256), 0, st, part, part2, n, S);
+    EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(fold)");
+    src = part2;
+    return 0;
+}
 int wgrad_reduce(float* part, float* dw, int C, int K, int S, hipStream_t st) {
     const long n = (long)9 * C * K;
-    const float* src = part;
-    int rows = S;
-    if (S > RG) {
-        float* part2 = part + (size_t)S * n;
-        rows = (S + RG - 1) / RG;
-        hipLaunchKernelGGL(wgrad_fold_kernel, dim3(egz_cdiv(n, 256), rows), dim3(256), 0, st, part, part2, n, S);
-        EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(fold)");
-        src = part2;
-    }
+    const float* src; int rows;
+    if (const int e = wgrad_fold(part, n, S, st, src, rows)) return e;
     if (C % 8 == 0 && K % 32 == 0) {
         hipLaunchKernelGGL(wgrad_reduce_tile_kernel, dim3(C / 8, K / 32), dim3(256), 0, st, src, dw, C, K, rows);
     } else {
@@ -1499,6 +1504,35 @@ int wgrad_reduce(float* part, float* dw, int C, int K, int S, hipStream_t st) {
     EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(reduce)");
     return 0;
 }
+// the phase forms: partials of 16 (phase, tap) tiles, folded into the 9 taps by the final pass
+int wgrad_reduce_ups(float* part, float* dw, int C, int K, int S, hipStream_t st) {
+    const long n = (long)9 * C * K;
+    const float* src; int rows;
+    if (const int e = wgrad_fold(part, 16L * C * K, S, st, src, rows)) return e;
+    const int g = egz_cdiv(n, 256) > 4096 ? 4096 : egz_cdiv(n, 256);
+    hipLaunchKernelGGL(wgrad_reduce_ups_kernel, dim3(g), dim3(256), 0, st, src, dw, C, K, rows);
+    EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(reduce-ups)");
+    return 0;
+}
+
+// Flags of egz_conv3x3_wgrad / egz_conv3x3_wgrad_ws_bytes (include/egaze_hip.h has the same list).
+enum : int {
+    WG_UPS = 1,             // the conv input was the nearest-x2 upsampling of x ([B][H/2][W/2][C])
+    WG_BT64 = 0x100,        // A/B: per-tap kernel on 64 tiles where it would take 128
+    WG_PERTAP = 0x800,      // A/B: force the per-tap kernel
+    WG_FOLD9 = 0x1000,      // A/B: the folded 9-tap form of an upsampled conv in place of its phase form
+    // split-half arithmetic on the 16-bit MFMA path (without it, and where no split-half kernel covers the geometry, exact f32): bf16 x3
+    // (16 bits, no scaling) when dy_absmax is NULL, f16 x3 (22 bits) with dy scaled by absmax_scale(*dy_absmax) when it is given; x_absmax
+    // (optional, f16 x3 only): max |x| -- x is scaled the same way (activations outside [2^-3, 6e4] otherwise leave the pair's 22-bit domain)
+    WG_SPLIT = 0x2000,
+    WG_NINETILE = 0x4000,   // A/B: K = 4 / 8 on the narrow kernel keep the nine-tile form, not (tap, k) pairs as columns
+    WG_XPRE = 0x8000,       // x holds pre-split activations (see conv3x3_wgrad9_x3_kernel) -- only where that kernel runs
+    WG_DPRE = 0x10000,      // dy holds pre-split pairs, scaled by the bound in *dy_absmax -- likewise
+    // with f16 split halves (dy_absmax given): TWO products per MAC instead of three, x_hi dy_hi + x_hi dy_lo -- x enters with
+    // its hi half only, rounded to nearest (11 significant bits of x, 22 of dy; per-element error ~2^-12 instead of 2^-22;
+    // egz_f16p2 in egz_common.h).  On the wide and the narrow split-half kernels; ignored by bf16 and exact-f32 launches.
+    WG_P2 = 0x20000,
+};
 
 int pick_splits(long M, int C, int K, int BT) {
     const long tiles = (long)((C + BT - 1) / BT) * ((K + BT - 1) / BT) * 9;
@@ -1511,7 +1545,7 @@ int pick_splits(long M, int C, int K, int BT) {
 
 // segment length of the upsample-phase kernel on the LOW-res row (0 = not applicable)
 int pick_seg_ups(int W, int C, int K, int flags) {
-    if ((flags & 0x1800) || C % 64 != 0 || K % 64 != 0 || W % 2) return 0;   // 0x1000: force the folded 9-tap form
+    if ((flags & (WG_PERTAP | WG_FOLD9)) || C % 64 != 0 || K % 64 != 0 || W % 2) return 0;
     const int Wl = W / 2;
     if (Wl % 32 == 0) return 32;
     if (Wl % 28 == 0) return 28;
@@ -1529,7 +1563,7 @@ int pick_splits_ups(long nseg, int C, int K) {
 
 // segment length of the 9-tap fused kernel (0 = not applicable -> per-tap kernel)
 int pick_seg(int W, int C, int K, int flags) {
-    if (flags & 0x800) return 0;                      // force the per-tap kernel (A/B benchmarking)
+    if (flags & WG_PERTAP) return 0;
     if (C % 64 != 0 || K % 64 != 0) return 0;
     if (W % 32 == 0) return 32;
     if (W % 28 == 0) return 28;
@@ -1545,11 +1579,11 @@ int pick_splits9(long nseg, int C, int K, int target = 1024) {
     return (int)s;
 }
 
-// split-half 9-tap kernel (flags 0x2000): patch width (0 = not applicable); rows narrower than the patch are masked
+// split-half 9-tap kernel (WG_SPLIT): patch width (0 = not applicable); rows narrower than the patch are masked
 int pick_patch_x3(int W, int C, int K, int flags) {
-    if (!(flags & 0x2000) || (flags & 0x800) || C % 32 != 0) return 0;
-    if (K % 64 != 0 && ((flags & 1) || K > 64 || K % 4 != 0)) return 0;   // K < 64 (late-fusion widths): plain form, masked k-tile
-    if (C % 64 != 0 && ((flags & 1) || C != 32)) return 0;       // C = 32 (padded first conv): plain 9-tap form, half c-tile
+    if (!(flags & WG_SPLIT) || (flags & WG_PERTAP) || C % 32 != 0) return 0;
+    if (K % 64 != 0 && ((flags & WG_UPS) || K > 64 || K % 4 != 0)) return 0;   // K < 64 (late-fusion widths): plain form, masked k-tile
+    if (C % 64 != 0 && ((flags & WG_UPS) || C != 32)) return 0;  // C = 32 (padded first conv): plain 9-tap form, half c-tile
     // Large images: the 4 x 8 patch.  A stage stages the patch's halo, (R + 2) x (WD + 2) pixels for 32 outputs: 3.2x for 1 x 32,
     // 2.25x for 2 x 16, 1.9x for 4 x 8 -- and every staged element costs a fetch from L2 and an f16 split.  On the 224- and
     // 112-wide layers the squarer patch is 5-10 % faster (64 -> 64 @ 224: 474 -> 441 us, @ 224 decoder: 397 -> 358, 128 -> 128
@@ -1566,7 +1600,7 @@ int pick_patch_x3(int W, int C, int K, int flags) {
 }
 // narrow split-half kernel (C, K <= 32, plain conv): run width of its 64-pixel patch (0 = not applicable)
 int pick_narrow_x3(int W, int C, int K, int flags) {
-    if (!(flags & 0x2000) || (flags & 0x801) || C > 32 || K > 32) return 0;
+    if (!(flags & WG_SPLIT) || (flags & (WG_PERTAP | WG_UPS)) || C > 32 || K > 32) return 0;
     // (a 4 x 16 patch where a 2 x 32 one fits measured the same on the late-fusion step: 1.30 vs 1.31 ms)
     return (W % 32 == 0) ? 32 : (W % 16 == 0) ? 16 : 0;
 }
@@ -1580,235 +1614,199 @@ long npatch_x3(int B, int H, int W, int WD) { return (long)B * ((H + 32 / WD - 1
 
 int pick_bt(int C, int K, int flags) {
     if (C % 64 != 0 || K % 64 != 0) return 32;
-    if (flags & 0x100) return 64;
+    if (flags & WG_BT64) return 64;
     return (C % 128 == 0 && K % 128 == 0) ? 128 : 64;
+}
+
+// The split-half kernels fetch through 32-bit buffer offsets: true when an operand (x with its halo row, or dy) has 4 GiB or more.
+bool wgrad_over_4g(int B, int H, int W, int C, int K, bool ups) {
+    const unsigned long long xb = 4ull * B * (ups ? H / 2 : H) * (ups ? W / 2 : W) * C + 4ull * (W + 1) * C;
+    const unsigned long long db = 4ull * B * H * W * K;
+    return xb >= (1ull << 32) || db >= (1ull << 32);
+}
+
+// Which kernel family takes a weight gradient, and its launch geometry: what egz_conv3x3_wgrad launches and what
+// egz_conv3x3_wgrad_ws_bytes sizes.  The order below is the order of preference.
+enum class Route {
+    UPS_X3,     // split-half phase form of an upsampled conv, patches on the low-res grid
+    NARROW,     // late-fusion widths (C, K <= 32): one 32 x 32 tile, waves split the pixels
+    PATCH9,     // split-half (bf16 x3 / f16 x3) 9-tap kernel on the 16-bit MFMA path
+    UPS_F32,    // phase-decomposed upsample in f32: 4/9 of the MACs
+    SEG9,       // 9-tap kernel on row segments, f32
+    PER_TAP,    // one f32 GEMM per tap
+};
+struct WgradPlan {
+    Route route;
+    int flags;  // without WG_SPLIT where an operand is too large for it: exact-f32 kernels (64-bit addressing)
+    int geo;    // patch width WD (UPS_X3, NARROW, PATCH9), segment length (UPS_F32, SEG9) or tile size BT (PER_TAP)
+    int S;      // splits
+    long per;   // patches / segments / pixels per split
+    long n;     // floats per partial: 9 C K, or 16 C K (phase, tap) tiles in the phase forms
+    dim3 grid;
+};
+WgradPlan wgrad_plan(int B, int H, int W, int C, int K, int flags) {
+    const bool ups = flags & WG_UPS;
+    if ((flags & WG_SPLIT) && wgrad_over_4g(B, H, W, C, K, ups)) flags &= ~WG_SPLIT;
+    WgradPlan p{Route::PER_TAP, flags, 0, 1, 0, 9L * C * K, dim3()};
+    long units;                                                 // patches / segments / pixels in all
+    int tiles = ((C + 63) / 64) * ((K + 63) / 64), gz = 1;
+    if (ups && !(flags & WG_FOLD9) && H % 2 == 0 && W % 2 == 0 && (p.geo = pick_patch_x3(W / 2, C, K, flags))) {
+        p.route = Route::UPS_X3, p.n = 16L * C * K, gz = 2;     // two row-phase blocks per (tile, split)
+        p.S = pick_splits9(units = npatch_x3(B, H / 2, W / 2, p.geo), C, K, X3_BLOCKS / 2);
+    } else if ((p.geo = pick_narrow_x3(W, C, K, flags))) {
+        p.route = Route::NARROW, tiles = 1;
+        p.S = pick_splits9(units = npatch_x3n(B, H, W, p.geo), C, K, X3_BLOCKS);
+    } else if ((p.geo = pick_patch_x3(W, C, K, flags))) {
+        p.route = Route::PATCH9;
+        p.S = pick_splits9(units = npatch_x3(B, H, W, p.geo), C, K, X3_BLOCKS);
+    } else if (ups && (p.geo = pick_seg_ups(W, C, K, flags))) {
+        p.route = Route::UPS_F32, p.n = 16L * C * K, gz = 4;    // 16 (phase, tap) partial tiles per split
+        p.S = pick_splits_ups(units = (long)B * (H / 2) * (W / 2 / p.geo), C, K);
+    } else if ((p.geo = pick_seg(W, C, K, flags))) {
+        p.route = Route::SEG9;
+        p.S = pick_splits9(units = (long)B * H * (W / p.geo), C, K);
+    } else {
+        p.geo = pick_bt(C, K, flags);
+        tiles = ((C + p.geo - 1) / p.geo) * ((K + p.geo - 1) / p.geo) * 9;
+        p.S = pick_splits(units = (long)B * H * W, C, K, p.geo);
+    }
+    p.per = (units + p.S - 1) / p.S;
+    if (p.route == Route::PER_TAP) p.per = (p.per + PK - 1) / PK * PK;
+    p.grid = dim3(tiles, p.S, gz);
+    return p;
+}
+
+struct WgradArgs {   // what a weight-gradient launch is given, whichever kernel takes it; x_absmax is NULL unless dy_absmax is given
+    const float* x; const float* dy; float* part; int B, H, W, C, K;
+    const unsigned int* dy_absmax; const unsigned int* x_absmax; const float* x_bn; hipStream_t st;
+};
+// the one place that spells out the arguments the kernels share; tail: what the split-half kernels take besides
+template <typename Kern, typename... Tail>
+void wgrad_launch(Kern kern, const WgradArgs& a, const WgradPlan& p, Tail... tail) {
+    hipLaunchKernelGGL(kern, p.grid, dim3(256), 0, a.st, a.x, a.dy, a.part, a.B, a.H, a.W, a.C, a.K, p.per, tail...);
+}
+
+// run-time value -> template argument: a resolver picks the tag and hands it on; resolve(go, r1, r2, ...) calls go(tag1, tag2, ...)
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename T> struct TypeTag { using type = T; };
+template <int R_, int WD_> struct Patch { static constexpr int R = R_, WD = WD_; };
+template <typename F> void resolve(F&& go) { go(); }
+template <typename F, typename R, typename... Rs> void resolve(F&& go, R&& r, Rs&&... rs) {
+    r([&](auto tag) { resolve([&](auto... rest) { go(tag, rest...); }, rs...); });
+}
+auto by_bool(bool b) { return [b](auto&& k) { if (b) k(std::true_type{}); else k(std::false_type{}); }; }
+// operand type of the split-half kernels: bf16 x3 without dy_absmax, f16 x3 with it, two products per MAC under WG_P2
+auto by_type(const WgradArgs& a, int flags) {
+    return [f16 = a.dy_absmax != nullptr, p2 = (flags & WG_P2) != 0](auto&& k) {
+        if (!f16) k(TypeTag<__bf16>{}); else if (p2) k(TypeTag<egz_f16p2>{}); else k(TypeTag<_Float16>{});
+    };
+}
+auto by_patch(int WD) {          // the 32-pixel patches of the wide kernels: 1 x 32, 2 x 16, 4 x 8
+    return [WD](auto&& k) { if (WD == 32) k(Patch<1, 32>{}); else if (WD == 16) k(Patch<2, 16>{}); else k(Patch<4, 8>{}); };
+}
+// ... and the 64-pixel patches of the narrow kernels: 2 x 32, 4 x 16
+auto by_narrow_patch(int WD) { return [WD](auto&& k) { if (WD == 32) k(Patch<2, 32>{}); else k(Patch<4, 16>{}); }; }
+auto by_seg(int L) { return [L](auto&& k) { if (L == 32) k(Int<32>{}); else if (L == 28) k(Int<28>{}); else k(Int<14>{}); }; }
+
+void launch_ups_x3(const WgradArgs& a, const WgradPlan& p) {
+    resolve([&](auto t, auto pt) {
+        wgrad_launch(conv3x3_wgrad_ups_x3_kernel<typename decltype(t)::type, decltype(pt)::R, decltype(pt)::WD>, a, p, a.dy_absmax, a.x_absmax);
+    }, by_type(a, p.flags), by_patch(p.geo));
+}
+void launch_narrow(const WgradArgs& a, const WgradPlan& p) {
+    // few filters: (tap, k) pairs as GEMM columns.  The kernel fetches dy as one float4 per k-quad at a pixel stride of 4 K
+    // bytes: K is 4 or 8 here (K % 4 == 0 is an argument check of the entry point)
+    const bool tappack = (a.K == 4 || a.K == 8) && !(p.flags & WG_NINETILE);
+    resolve([&](auto t, auto pt, auto bn, auto tp) {
+        using T = typename decltype(t)::type;
+        using P = decltype(pt);
+        constexpr bool BNIN = decltype(bn)::value;
+        if constexpr (decltype(tp)::value)
+            wgrad_launch(conv3x3_wgrad9_x3t_kernel<T, P::R, P::WD, BNIN>, a, p, a.dy_absmax, a.x_absmax, a.x_bn);
+        else
+            wgrad_launch(conv3x3_wgrad9_x3n_kernel<T, P::R, P::WD, BNIN>, a, p, a.dy_absmax, a.x_absmax, a.x_bn);
+    }, by_type(a, p.flags), by_narrow_patch(p.geo), by_bool(a.x_bn != nullptr), by_bool(tappack));
+}
+void launch_patch9(const WgradArgs& a, const WgradPlan& p) {
+    resolve([&](auto t, auto pt, auto u, auto xp, auto dp) {
+        using T = typename decltype(t)::type;
+        using P = decltype(pt);
+        constexpr bool UPS = decltype(u)::value, XPRE = decltype(xp)::value, DPRE = decltype(dp)::value;
+        // pre-split operands exist only for f16 x3 (three or two products) on a plain conv: the entry point lets no other through
+        if constexpr (!(XPRE || DPRE) || (!UPS && !std::is_same<T, __bf16>::value))
+            wgrad_launch(conv3x3_wgrad9_x3_kernel<T, UPS, P::R, P::WD, XPRE, DPRE>, a, p, a.dy_absmax, a.x_absmax);
+    }, by_type(a, p.flags), by_patch(p.geo), by_bool(p.flags & WG_UPS), by_bool(p.flags & WG_XPRE), by_bool(p.flags & WG_DPRE));
+}
+void launch_ups_f32(const WgradArgs& a, const WgradPlan& p) {
+    resolve([&](auto l) { wgrad_launch(conv3x3_wgrad_ups_kernel<decltype(l)::value>, a, p); }, by_seg(p.geo));
+}
+void launch_seg9(const WgradArgs& a, const WgradPlan& p) {
+    resolve([&](auto u, auto l) { wgrad_launch(conv3x3_wgrad9_kernel<decltype(u)::value, decltype(l)::value>, a, p); },
+            by_bool(p.flags & WG_UPS), by_seg(p.geo));
+}
+void launch_per_tap(const WgradArgs& a, const WgradPlan& p) {
+    resolve([&](auto u) {
+        constexpr bool UPS = decltype(u)::value;
+        if (p.geo == 32) wgrad_launch(conv3x3_wgrad32_kernel<UPS>, a, p);
+        else if (p.geo == 128) wgrad_launch(conv3x3_wgrad_kernel<128, UPS>, a, p);
+        else wgrad_launch(conv3x3_wgrad_kernel<64, UPS>, a, p);
+    }, by_bool(p.flags & WG_UPS));
 }
 
 }  // namespace
 
 EGZ_API size_t egz_conv3x3_wgrad_ws_bytes(int B, int H, int W, int C, int K, int flags) {
-    if (flags & 0x2000) {   // same size rule as egz_conv3x3_wgrad
-        const bool ups = flags & 1;
-        const unsigned long long xb = 4ull * B * (ups ? H / 2 : H) * (ups ? W / 2 : W) * C + 4ull * (W + 1) * C;
-        const unsigned long long db = 4ull * B * H * W * K;
-        if (xb >= (1ull << 32) || db >= (1ull << 32)) flags &= ~0x2000;
-    }
-    const int L = pick_seg(W, C, K, flags);
-    const long n = (long)9 * C * K;
-    if ((flags & 1) && !(flags & 0x1000) && H % 2 == 0 && W % 2 == 0) {
-        if (const int WD = pick_patch_x3(W / 2, C, K, flags))       // phase form on the low-res grid, 16 partial tiles
-            return wgrad_ws_floats(pick_splits9(npatch_x3(B, H / 2, W / 2, WD), C, K, X3_BLOCKS / 2), 16L * C * K) * sizeof(float);
-    }
-    if (const int WD = pick_narrow_x3(W, C, K, flags))
-        return wgrad_ws_floats(pick_splits9(npatch_x3n(B, H, W, WD), C, K, X3_BLOCKS), n) * sizeof(float);
-    if (const int WD = pick_patch_x3(W, C, K, flags))
-        return wgrad_ws_floats(pick_splits9(npatch_x3(B, H, W, WD), C, K, X3_BLOCKS), n) * sizeof(float);
-    if (flags & 1) {
-        const int Lu = pick_seg_ups(W, C, K, flags);
-        if (Lu) return wgrad_ws_floats(pick_splits_ups((long)B * (H / 2) * (W / 2 / Lu), C, K), 16L * C * K) * sizeof(float);
-    }
-    if (L) return wgrad_ws_floats(pick_splits9((long)B * H * (W / L), C, K), n) * sizeof(float);
-    const int bt = pick_bt(C, K, flags);
-    const int S = pick_splits((long)B * H * W, C, K, bt);
-    return wgrad_ws_floats(S, n) * sizeof(float);
+    const WgradPlan p = wgrad_plan(B, H, W, C, K, flags);
+    return wgrad_ws_floats(p.S, p.n) * sizeof(float);
 }
 
-// flags: bit0 = the conv input was the nearest-x2 upsampling of x ([B][H/2][W/2][C]); 0x100 forces 64 tiles;
-//        0x800 forces the per-tap kernel, 0x1000 the folded 9-tap form of an upsampled conv (A/B benchmarking);
-//        0x2000 = split-half arithmetic on the 16-bit MFMA path (C, K multiples of 64; else exact f32): bf16 x3 (16 bits,
-//        no scaling) when dy_absmax is NULL, f16 x3 (22 bits) with dy scaled by absmax_scale(*dy_absmax) when it is given;
-//        x_absmax (optional, f16 x3 only): max |x| -- x is scaled the same way (activations outside [2^-3, 6e4] otherwise
-//        leave the f16 pair's 22-bit domain).
-//        0x20000 = with f16 split halves: TWO products per MAC instead of three -- x's lo half is not multiplied (11 significant
-//        bits of x, rounded to nearest; 22 of dy; per-element error ~2^-12 instead of 2^-22) -- on conv3x3_wgrad9_x3_kernel / conv3x3_wgrad_ups_x3_kernel.
-// x: conv input (NHWC), dy: gradient of the conv output ([B][H][W][K]), dw: (K, C, 3, 3) like the reference.
-// 1 when a plain split-half weight gradient of this geometry runs on the narrow kernel (C, K <= 32, W % 16 == 0, 32-bit
-// buffer offsets) -- the only one that takes a deferred-BatchNorm activation operand (x_bn)
-// 1 when egz_conv3x3_wgrad(flags 0x2000 [| 0x8000]) of a plain conv runs on conv3x3_wgrad9_x3_kernel, i.e. can take a pre-split
-// x operand: C, K multiples of 64, a patch geometry for this width, operands below 4 GiB.
+// 1 when egz_conv3x3_wgrad(WG_SPLIT) of a plain conv runs on conv3x3_wgrad9_x3_kernel, i.e. can take a pre-split x (WG_XPRE)
+// or dy (WG_DPRE) operand: C, K multiples of 64, a patch geometry for this width, operands below 4 GiB.
 EGZ_API int egz_conv3x3_wgrad_presplit_ok(int B, int H, int W, int C, int K) {
     if (B <= 0 || H <= 0 || W <= 0 || C % 64 != 0 || K % 64 != 0) return 0;
-    const unsigned long long xb = 4ull * B * H * W * C + 4ull * (W + 1) * C, db = 4ull * B * H * W * K;
-    if (xb >= (1ull << 32) || db >= (1ull << 32)) return 0;
-    return pick_patch_x3(W, C, K, 0x2000) != 0;
+    if (wgrad_over_4g(B, H, W, C, K, false)) return 0;
+    return pick_patch_x3(W, C, K, WG_SPLIT) != 0;
 }
 
+// 1 when a plain split-half weight gradient of this geometry runs on the narrow kernel (C, K <= 32, W % 16 == 0, 32-bit
+// buffer offsets) -- the only one that takes a deferred-BatchNorm activation operand (x_bn).
 EGZ_API int egz_conv3x3_wgrad_narrow_ok(int B, int H, int W, int C, int K) {
     if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || K <= 0 || C % 4 || K % 4) return 0;
-    const unsigned long long xb = 4ull * B * H * W * C + 4ull * (W + 1) * C, db = 4ull * B * H * W * K;
-    if (xb >= (1ull << 32) || db >= (1ull << 32)) return 0;
-    return pick_narrow_x3(W, C, K, 0x2000) ? 1 : 0;
+    if (wgrad_over_4g(B, H, W, C, K, false)) return 0;
+    return pick_narrow_x3(W, C, K, WG_SPLIT) ? 1 : 0;
 }
 
+// x: conv input (NHWC), dy: gradient of the conv output ([B][H][W][K]), dw: (K, C, 3, 3) like the reference; flags: WG_*.
 // x_bn (optional, narrow geometry only): x is the PRE-BatchNorm output of the block below and x_bn that BatchNorm's 4 x C
 // coefficient rows (mean, 1/std, scale, shift); relu(x * scale + shift) is applied while x is staged, x_absmax = its max.
 EGZ_API int egz_conv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int C, int K,
                               int flags, void* workspace, size_t ws_bytes, const unsigned int* dy_absmax,
                               const unsigned int* x_absmax, const float* x_bn, hipStream_t st) {
     EGZ_CHECK_ARG(x && dy && dw && workspace, "egz_conv3x3_wgrad: null pointer");
-    EGZ_CHECK_ARG(!x_bn || ((flags & 0x2000) && egz_conv3x3_wgrad_narrow_ok(B, H, W, C, K) && pick_narrow_x3(W, C, K, flags)),
+    // (narrow_ok first: it vouches for the C, K > 0 that a plan needs)
+    EGZ_CHECK_ARG(!x_bn || (egz_conv3x3_wgrad_narrow_ok(B, H, W, C, K) && wgrad_plan(B, H, W, C, K, flags).route == Route::NARROW),
                   "egz_conv3x3_wgrad: a deferred-BatchNorm operand (x_bn) exists on the narrow split-half kernel only "
                   "(C, K <= 32, W %% 16 == 0, plain conv)");
     EGZ_CHECK_ARG(C % 4 == 0 && K % 4 == 0 && C > 0 && K > 0, "egz_conv3x3_wgrad: C=%d K=%d must be multiples of 4", C, K);
-    const bool ups = flags & 1;
+    const bool ups = flags & WG_UPS;
     EGZ_CHECK_ARG(!ups || (H % 2 == 0 && W % 2 == 0), "egz_conv3x3_wgrad: upsampled output must be even");
-    const long M = (long)B * H * W;
-    if (flags & 0x2000) {   // split-half kernels fetch through 32-bit buffer offsets
-        const unsigned long long xb = 4ull * B * (ups ? H / 2 : H) * (ups ? W / 2 : W) * C + 4ull * (W + 1) * C;
-        const unsigned long long db = 4ull * B * H * W * K;
-        if (xb >= (1ull << 32) || db >= (1ull << 32)) flags &= ~0x2000;      // too large: exact-f32 kernels (64-bit addressing)
-    }
-    // flags 0x8000: x holds pre-split activations (see conv3x3_wgrad9_x3_kernel) -- only where that kernel runs
-    const bool xpre = (flags & 0x8000) != 0, dpre = (flags & 0x10000) != 0;
-    // 0x20000: two products per MAC on the split-half f16 kernels of the wide layers (x_hi dy_hi + x_hi dy_lo: x enters with its hi
-    // half only, rounded to nearest; egz_f16p2 in egz_common.h).  Also on the narrow (late-fusion) kernels; ignored by bf16 and exact-f32 launches.
-    const bool p2 = (flags & 0x20000) != 0 && dy_absmax;
-    EGZ_CHECK_ARG(!(xpre || dpre) || (egz_conv3x3_wgrad_presplit_ok(B, H, W, C, K) && (flags & 0x2000) && !ups && dy_absmax && x_absmax && !x_bn),
+    const WgradPlan p = wgrad_plan(B, H, W, C, K, flags);
+    EGZ_CHECK_ARG(!(flags & (WG_XPRE | WG_DPRE)) ||
+                      (egz_conv3x3_wgrad_presplit_ok(B, H, W, C, K) && (p.flags & WG_SPLIT) && !ups && dy_absmax && x_absmax && !x_bn),
                   "egz_conv3x3_wgrad: a pre-split x / dy operand (flags 0x8000 / 0x10000) needs the split-half 9-tap kernel's geometry "
                   "(egz_conv3x3_wgrad_presplit_ok), f16 x3 (dy_absmax, x_absmax) and a plain conv");
-    float* part = static_cast<float*>(workspace);
-    const long nred = (long)9 * C * K;
-    if (ups && !(flags & 0x1000)) {
-        if (const int WD = pick_patch_x3(W / 2, C, K, flags)) {     // split-half phase form of an upsampled conv
-            const long n16 = 16L * C * K;
-            const long np = npatch_x3(B, H / 2, W / 2, WD);
-            const int S = pick_splits9(np, C, K, X3_BLOCKS / 2);    // two row-phase blocks per (tile, split)
-            EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(S, n16) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
-            const int pps = (int)((np + S - 1) / S);
-            dim3 grid((C / 64) * (K / 64), S, 2);
-#define EGZ_WUX(TT, RR, WW) hipLaunchKernelGGL((conv3x3_wgrad_ups_x3_kernel<TT, RR, WW>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, dy_absmax ? x_absmax : nullptr)
-            if (dy_absmax && p2) { if (WD == 32) EGZ_WUX(egz_f16p2, 1, 32); else if (WD == 16) EGZ_WUX(egz_f16p2, 2, 16); else EGZ_WUX(egz_f16p2, 4, 8); }
-            else if (dy_absmax) { if (WD == 32) EGZ_WUX(_Float16, 1, 32); else if (WD == 16) EGZ_WUX(_Float16, 2, 16); else EGZ_WUX(_Float16, 4, 8); }
-            else           { if (WD == 32) EGZ_WUX(__bf16, 1, 32); else if (WD == 16) EGZ_WUX(__bf16, 2, 16); else EGZ_WUX(__bf16, 4, 8); }
-#undef EGZ_WUX
-            EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(ups-phase split)");
-            const float* src = part;
-            int rows = S;
-            if (S > RG) {
-                float* part2 = part + (size_t)S * n16;
-                rows = (S + RG - 1) / RG;
-                hipLaunchKernelGGL(wgrad_fold_kernel, dim3(egz_cdiv(n16, 256), rows), dim3(256), 0, st, part, part2, n16, S);
-                EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(fold)");
-                src = part2;
-            }
-            const int g = egz_cdiv(nred, 256) > 4096 ? 4096 : egz_cdiv(nred, 256);
-            hipLaunchKernelGGL(wgrad_reduce_ups_kernel, dim3(g), dim3(256), 0, st, src, dw, C, K, rows);
-            EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(reduce-ups)");
-            return 0;
-        }
+    EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(p.S, p.n) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
+    const WgradArgs a{x, dy, static_cast<float*>(workspace), B, H, W, C, K, dy_absmax, dy_absmax ? x_absmax : nullptr, x_bn, st};
+    const char* what = "egz_conv3x3_wgrad";
+    bool phases = false;                // 16 (phase, tap) tiles per partial
+    switch (p.route) {
+    case Route::UPS_X3:  launch_ups_x3(a, p),  what = "egz_conv3x3_wgrad(ups-phase split)", phases = true; break;
+    case Route::NARROW:  launch_narrow(a, p),  what = "egz_conv3x3_wgrad(9-tap split, narrow)"; break;
+    case Route::PATCH9:  launch_patch9(a, p),  what = "egz_conv3x3_wgrad(9-tap split)"; break;
+    case Route::UPS_F32: launch_ups_f32(a, p), what = "egz_conv3x3_wgrad(ups-phase)", phases = true; break;
+    case Route::SEG9:    launch_seg9(a, p),    what = "egz_conv3x3_wgrad(9-tap)"; break;
+    case Route::PER_TAP: launch_per_tap(a, p); break;
     }
-    if (const int WD = pick_narrow_x3(W, C, K, flags)) {  // late-fusion widths: one 32 x 32 tile, waves split the pixels
-        const long np = npatch_x3n(B, H, W, WD);
-        const int S = pick_splits9(np, C, K, X3_BLOCKS);
-        EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(S, nred) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
-        const int pps = (int)((np + S - 1) / S);
-        dim3 grid(1, S);
-#define EGZ_W9N(TT, RR, WW)                                                                                                   \
-        do {                                                                                                                  \
-            if (x_bn) hipLaunchKernelGGL((conv3x3_wgrad9_x3n_kernel<TT, RR, WW, true>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, dy_absmax ? x_absmax : nullptr, x_bn); \
-            else      hipLaunchKernelGGL((conv3x3_wgrad9_x3n_kernel<TT, RR, WW, false>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, dy_absmax ? x_absmax : nullptr, x_bn); \
-        } while (0)
-#define EGZ_W9T(TT, RR, WW)                                                                                                   \
-        do {                                                                                                                  \
-            if (x_bn) hipLaunchKernelGGL((conv3x3_wgrad9_x3t_kernel<TT, RR, WW, true>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, dy_absmax ? x_absmax : nullptr, x_bn); \
-            else      hipLaunchKernelGGL((conv3x3_wgrad9_x3t_kernel<TT, RR, WW, false>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, dy_absmax ? x_absmax : nullptr, x_bn); \
-        } while (0)
-        // few filters: (tap, k) pairs as GEMM columns (0x4000 keeps the nine-tile form: A/B runs).  The kernel fetches dy as one float4
-        // per k-quad at a pixel stride of 4 K bytes: K is 4 or 8 here (K % 4 == 0 is an argument check above)
-        if ((K == 4 || K == 8) && !(flags & 0x4000)) {
-            if (dy_absmax && p2) { if (WD == 32) EGZ_W9T(egz_f16p2, 2, 32); else EGZ_W9T(egz_f16p2, 4, 16); }
-            else if (dy_absmax) { if (WD == 32) EGZ_W9T(_Float16, 2, 32); else EGZ_W9T(_Float16, 4, 16); }
-            else           { if (WD == 32) EGZ_W9T(__bf16, 2, 32); else EGZ_W9T(__bf16, 4, 16); }
-        } else
-        if (dy_absmax && p2) { if (WD == 32) EGZ_W9N(egz_f16p2, 2, 32); else EGZ_W9N(egz_f16p2, 4, 16); }
-        else if (dy_absmax) { if (WD == 32) EGZ_W9N(_Float16, 2, 32); else EGZ_W9N(_Float16, 4, 16); }
-        else           { if (WD == 32) EGZ_W9N(__bf16, 2, 32); else EGZ_W9N(__bf16, 4, 16); }
-#undef EGZ_W9T
-#undef EGZ_W9N
-        EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(9-tap split, narrow)");
-        return wgrad_reduce(part, dw, C, K, S, st);
-    }
-    if (const int WD = pick_patch_x3(W, C, K, flags)) {   // split-half (bf16 x3 / f16 x3) on the 16-bit MFMA path
-        const long np = npatch_x3(B, H, W, WD);
-        const int S = pick_splits9(np, C, K, X3_BLOCKS);
-        EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(S, nred) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
-        const int pps = (int)((np + S - 1) / S);
-        dim3 grid(((C + 63) / 64) * ((K + 63) / 64), S);
-#define EGZ_W9X(TT, U, RR, WW) hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<TT, U, RR, WW>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, dy_absmax ? x_absmax : nullptr)
-#define EGZ_W9QT(TT, RR, WW, XP, DP) hipLaunchKernelGGL((conv3x3_wgrad9_x3_kernel<TT, false, RR, WW, XP, DP>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps, dy_absmax, x_absmax)
-#define EGZ_W9Q(RR, WW, XP, DP) do { if (p2) EGZ_W9QT(egz_f16p2, RR, WW, XP, DP); else EGZ_W9QT(_Float16, RR, WW, XP, DP); } while (0)
-#define EGZ_W9P(RR, WW) do { if (xpre && dpre) EGZ_W9Q(RR, WW, true, true); else if (xpre) EGZ_W9Q(RR, WW, true, false); else EGZ_W9Q(RR, WW, false, true); } while (0)
-#define EGZ_W9T(TT)                                                                                                    \
-        if (ups) { if (WD == 32) EGZ_W9X(TT, true, 1, 32); else if (WD == 16) EGZ_W9X(TT, true, 2, 16); else EGZ_W9X(TT, true, 4, 8); } \
-        else     { if (WD == 32) EGZ_W9X(TT, false, 1, 32); else if (WD == 16) EGZ_W9X(TT, false, 2, 16); else EGZ_W9X(TT, false, 4, 8); }
-        if (xpre || dpre) {        // pre-split x (flags 0x8000) and / or dy (0x10000) operand: f16 x3, plain conv
-            if (WD == 32) EGZ_W9P(1, 32); else if (WD == 16) EGZ_W9P(2, 16); else EGZ_W9P(4, 8);
-        } else
-        if (dy_absmax && p2) { EGZ_W9T(egz_f16p2) } else if (dy_absmax) { EGZ_W9T(_Float16) } else { EGZ_W9T(__bf16) }
-#undef EGZ_W9P
-#undef EGZ_W9Q
-#undef EGZ_W9QT
-#undef EGZ_W9T
-#undef EGZ_W9X
-        EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(9-tap split)");
-        return wgrad_reduce(part, dw, C, K, S, st);
-    }
-    const int Lu = ups ? pick_seg_ups(W, C, K, flags) : 0;
-    if (Lu) {      // phase-decomposed upsample: 16 (phase, tap) partial tiles per split, 4/9 of the MACs
-        const long n16 = 16L * C * K;
-        const long nseg = (long)B * (H / 2) * (W / 2 / Lu);
-        const int S = pick_splits_ups(nseg, C, K);
-        EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(S, n16) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
-        const int sps = (int)((nseg + S - 1) / S);
-        dim3 grid((C / 64) * (K / 64), S, 4);
-        if (Lu == 32)      hipLaunchKernelGGL(conv3x3_wgrad_ups_kernel<32>, grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, sps);
-        else if (Lu == 28) hipLaunchKernelGGL(conv3x3_wgrad_ups_kernel<28>, grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, sps);
-        else               hipLaunchKernelGGL(conv3x3_wgrad_ups_kernel<14>, grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, sps);
-        EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(ups-phase)");
-        const float* src = part;
-        int rows = S;
-        if (S > RG) {
-            float* part2 = part + (size_t)S * n16;
-            rows = (S + RG - 1) / RG;
-            hipLaunchKernelGGL(wgrad_fold_kernel, dim3(egz_cdiv(n16, 256), rows), dim3(256), 0, st, part, part2, n16, S);
-            EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(fold)");
-            src = part2;
-        }
-        const int g = egz_cdiv(nred, 256) > 4096 ? 4096 : egz_cdiv(nred, 256);
-        hipLaunchKernelGGL(wgrad_reduce_ups_kernel, dim3(g), dim3(256), 0, st, src, dw, C, K, rows);
-        EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(reduce-ups)");
-        return 0;
-    }
-    const int L = pick_seg(W, C, K, flags);
-    if (L) {
-        const long nseg = (long)B * H * (W / L);
-        const int S = pick_splits9(nseg, C, K);
-        EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(S, nred) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
-        const int sps = (int)((nseg + S - 1) / S);
-        dim3 grid((C / 64) * (K / 64), S);
-#define EGZ_W9(U, LL) hipLaunchKernelGGL((conv3x3_wgrad9_kernel<U, LL>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, sps)
-        if (ups) { if (L == 32) EGZ_W9(true, 32); else if (L == 28) EGZ_W9(true, 28); else EGZ_W9(true, 14); }
-        else     { if (L == 32) EGZ_W9(false, 32); else if (L == 28) EGZ_W9(false, 28); else EGZ_W9(false, 14); }
-#undef EGZ_W9
-        EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad(9-tap)");
-        return wgrad_reduce(part, dw, C, K, S, st);
-    }
-    const int bt = pick_bt(C, K, flags);
-    const int S = pick_splits(M, C, K, bt);
-    EGZ_CHECK_ARG(ws_bytes >= wgrad_ws_floats(S, nred) * sizeof(float), "egz_conv3x3_wgrad: workspace too small");
-    long pps = (M + S - 1) / S;
-    pps = (pps + PK - 1) / PK * PK;
-    dim3 grid(((C + bt - 1) / bt) * ((K + bt - 1) / bt) * 9, S);
-    if (bt == 32) {
-        if (ups) hipLaunchKernelGGL(conv3x3_wgrad32_kernel<true>, grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps);
-        else     hipLaunchKernelGGL(conv3x3_wgrad32_kernel<false>, grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps);
-    } else if (bt == 128) {
-        if (ups) hipLaunchKernelGGL((conv3x3_wgrad_kernel<128, true>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps);
-        else     hipLaunchKernelGGL((conv3x3_wgrad_kernel<128, false>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps);
-    } else {
-        if (ups) hipLaunchKernelGGL((conv3x3_wgrad_kernel<64, true>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps);
-        else     hipLaunchKernelGGL((conv3x3_wgrad_kernel<64, false>), grid, dim3(256), 0, st, x, dy, part, B, H, W, C, K, pps);
-    }
-    EGZ_CHECK_LAUNCH("egz_conv3x3_wgrad");
-    return wgrad_reduce(part, dw, C, K, S, st);
+    EGZ_CHECK_LAUNCH(what);
+    return phases ? wgrad_reduce_ups(a.part, dw, C, K, p.S, st) : wgrad_reduce(a.part, dw, C, K, p.S, st);
 }

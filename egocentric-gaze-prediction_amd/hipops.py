@@ -881,7 +881,12 @@ def colsum_f64(stat: torch.Tensor, ncols_out: int, out: Optional[torch.Tensor] =
     return res
 
 
-WGRAD_SPLIT = 0x2000       # egz_conv3x3_wgrad flag: split-half arithmetic (bf16 x3, or f16 x3 when dy_absmax is passed)
+# egz_conv3x3_wgrad flags (include/egaze_hip.h; P2_WGRAD above is the last of them)
+WGRAD_UPS = 1              # the conv input was the nearest-x2 upsampling of x
+WGRAD_BT64, WGRAD_PERTAP, WGRAD_FOLD9 = 0x100, 0x800, 0x1000      # A/B variants (variant_flag; tools/bench_conv.py --wflag)
+WGRAD_SPLIT = 0x2000       # split-half arithmetic (bf16 x3, or f16 x3 when dy_absmax is passed)
+WGRAD_NINETILE = 0x4000    # A/B: what WGRAD_TAPPACK = False sends
+WGRAD_XPRE, WGRAD_DPRE = 0x8000, 0x10000      # x / dy holds pre-split pairs
 
 
 WGRAD_TAPPACK = True      # K <= 8 filters on the narrow kernel: (tap, k) pairs as GEMM columns (False: nine zero-padded 32-column tiles;
@@ -897,7 +902,7 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, ups: bool = False, variant_
     B, H, W, K = dy.shape
     C = x.shape[3]
     dw = _out(out, (K, C, 3, 3), x.device)
-    flags = (1 if ups else 0) | variant_flag | (0 if WGRAD_TAPPACK else 0x4000)
+    flags = (WGRAD_UPS if ups else 0) | variant_flag | (0 if WGRAD_TAPPACK else WGRAD_NINETILE)
     am = xam = None
     prec = precision or PRECISION
     if prec in ("split", "split_bf16", "split_f16"):
@@ -911,13 +916,13 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, ups: bool = False, variant_
                 and LIB.egz_conv3x3_wgrad_presplit_ok(B, H, W, C, K)):
             raise RuntimeError("a pre-split activation reached a weight-gradient launch that cannot take it")
         xam = x._egz_absmax
-        flags |= 0x8000
+        flags |= WGRAD_XPRE
         PRESPLIT_STATS["wgrad"] += 1
     if dy_pre:     # dy holds pre-split pairs scaled by the bound in dy._egz_absmax (bn_relu_pool_bwd(presplit=...))
         if not (flags & WGRAD_SPLIT and am is not None and xam is not None and not ups and x_bn is None
                 and LIB.egz_conv3x3_wgrad_presplit_ok(B, H, W, C, K)):
             raise RuntimeError("a pre-split gradient reached a weight-gradient launch that cannot take it")
-        flags |= 0x10000
+        flags |= WGRAD_DPRE
         PRESPLIT_STATS["wgrad_dy"] += 1
     if BWD_PRODUCTS == 2 and am is not None:
         flags |= P2_WGRAD          # two products per MAC on the wide split-half kernels (ignored by the others)

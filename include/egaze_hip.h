@@ -133,9 +133,19 @@ size_t egz_conv3x3_wgrad_ws_bytes(int B, int H, int W, int C, int K, int flags);
 int egz_conv3x3_wgrad(const float* x, const float* dy, float* dw, int B, int H, int W, int C, int K, int flags,
                       void* workspace, size_t ws_bytes, const unsigned int* dy_absmax, const unsigned int* x_absmax,
                       const float* x_bn, hipStream_t stream);
-/* flags | 0x20000 (with 0x2000 and dy_absmax: f16 split halves on the wide kernels, C and K multiples of 32 / 64): TWO MFMA products
- * per MAC -- x_hi dy_hi + x_hi dy_lo: x enters with 11 significant bits, rounded to nearest (from the fp32 value, or from hi + lo
- * of a pre-split pair), dy keeps 22; dw moves by ~2e-4 relative L2.  Also on the narrow (late-fusion) kernels; ignored by the bf16 and exact-f32 launches. */
+/* flags (both entry points; the size query reads only those that choose the kernel):
+ *   1        the conv input was the nearest-x2 upsampling of x ([B][H/2][W/2][C]; H, W even)
+ *   0x2000   split-half arithmetic on the 16-bit MFMA path where a split-half kernel covers the geometry and both operands
+ *            are below 4 GiB (else exact f32): bf16 x3 when dy_absmax is NULL, f16 x3 with dy scaled by its abs-max when it is
+ *            given; x_absmax (optional, f16 x3 only): max |x|, x is scaled the same way
+ *   0x8000 / 0x10000   x / dy holds pre-split pairs (see egz_conv3x3_wgrad_presplit_ok below)
+ *   0x20000  with 0x2000 and dy_absmax (f16 split halves; wide kernels: C and K multiples of 32 / 64): TWO MFMA products
+ *            per MAC -- x_hi dy_hi + x_hi dy_lo: x enters with 11 significant bits, rounded to nearest (from the fp32 value, or
+ *            from hi + lo of a pre-split pair), dy keeps 22; dw moves by ~2e-4 relative L2.  Also on the narrow (late-fusion)
+ *            kernels; ignored by the bf16 and exact-f32 launches.
+ *   A/B benchmarking: 0x100 per-tap kernel on 64 tiles where it would take 128, 0x800 force the per-tap kernel, 0x1000 the
+ *            folded 9-tap form of an upsampled conv in place of its phase form, 0x4000 K = 4 / 8 on the narrow kernel keep
+ *            the nine-tile form */
 /* x_bn (optional): x is the PRE-BatchNorm conv output of the block below and x_bn that BatchNorm's 4 x C coefficient rows;
  * relu(x * scale + shift) is applied while x is staged (deferred BatchNorm, late_fusion.py:11-12), x_absmax = the max of the
  * normalised values.  Only where egz_conv3x3_wgrad_narrow_ok(B, H, W, C, K) (C, K <= 32, W % 16 == 0, flags 0x2000). */

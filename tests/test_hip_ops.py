@@ -1342,3 +1342,138 @@ def test_streamed_dispatch_splitk_leg(monkeypatch):
     assert st
     y, _ = h.conv3x3_fwd(xd, wp, b.to(DEV), 128, epi=h.EPI_BIAS_RELU, dtype=h.F16X3, streamed=True)
     assert rel(nchw(y), F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1))) < 2e-6
+
+
+# ----------------------------------------------------------------------------- weight gradient: every leg of the launch dispatch
+_WG_TYPES = {"f32": ("f32", 3), "bf16": ("split_bf16", 3), "f16": ("split_f16", 3), "f16p2": ("split_f16", 2)}      # precision, products
+_WG_X3 = ("bf16", "f16", "f16p2")
+_WG_TOL = {"f32": 1e-5, "bf16": 2e-5, "f16": 2e-6}         # test_conv3x3_wgrad_split; f16p2: the bars of test_backward_two_products
+_WG_PATCH = {"1x32": 32, "2x16": 16, "4x8": 24}            # patch of the wide split-half kernels -> the narrowest row that takes it
+
+
+def _wgrad_legs():
+    """(id, (H, W, C, K, ups), type, options).  H x W is the conv OUTPUT; B = 2 everywhere."""
+    legs = []
+    # phase form on split halves: low-res patches 1 x 32 / 2 x 16 / 4 x 8
+    for t in _WG_X3:
+        legs += [(f"upsx3-{p}-{t}", (hh, ww, 64, 64, True), t, {}) for p, (hh, ww) in (("1x32", (16, 64)), ("2x16", (16, 32)), ("4x8", (10, 48)))]
+    # narrow kernels: nine-tile form (K = 32; K = 8 with WGRAD_TAPPACK off) and tap-packed form (K = 8, 4) x patch x x_bn
+    for t in _WG_X3:
+        for p, ww in (("2x32", 32), ("4x16", 16)):
+            for bn in (False, True):
+                legs += [(f"narrow-{form}-{p}-{t}" + ("-bn" if bn else ""), (4, ww, 32, k, False), t, {"bn": bn, "tappack": tp})
+                         for form, k, tp in (("nine-k32", 32, True), ("nine-k8", 8, False), ("tap-k8", 8, True), ("tap-k4", 4, True))]
+    # 9-tap patch kernel: plain, upsampled through WGRAD_FOLD9, pre-split operands (f16 x3, three and two products)
+    for t in _WG_X3:
+        legs += [(f"patch9-{p}-{t}", (8, ww, 64, 64, False), t, {}) for p, ww in _WG_PATCH.items()]
+        legs += [(f"patch9-ups-{p}-{t}", (8, ww, 64, 64, True), t, {"flag": "WGRAD_FOLD9"}) for p, ww in _WG_PATCH.items()]
+    for t in ("f16", "f16p2"):
+        legs += [(f"patch9-{pre}-{p}-{t}", (8, ww, 64, 64, False), t, {"pre": pre}) for pre in ("xpre", "dpre", "xdpre") for p, ww in _WG_PATCH.items()]
+    # f32 routes: phase form on segments of 32 / 28 / 14 low-res pixels, 9-tap segments (upsampled: WGRAD_FOLD9), per-tap tiles
+    legs += [(f"f32-phase-{l}", (4, 2 * l, 64, 64, True), "f32", {}) for l in (32, 28, 14)]
+    for ups in (False, True):
+        u = "-ups" if ups else ""
+        legs += [(f"f32-seg9-{l}{u}", (4, l, 64, 64, ups), "f32", {"flag": "WGRAD_FOLD9"} if ups else {}) for l in (32, 28, 14)]
+        legs += [(f"f32-tap32{u}", (4, 12, 32, 64, ups), "f32", {}), (f"f32-tap64{u}", (4, 12, 64, 64, ups), "f32", {}),
+                 (f"f32-tap128{u}", (4, 12, 128, 128, ups), "f32", {}), (f"f32-tap64-forced{u}", (4, 12, 128, 128, ups), "f32", {"flag": "WGRAD_BT64"}),
+                 (f"f32-pertap-forced{u}", (4, 32, 64, 64, ups), "f32", {"flag": "WGRAD_PERTAP"})]
+    # more than 32 splits: wgrad_fold_kernel in front of the tile reduce, the generic reduce (K = 8) and the phase-form reduce
+    legs += [("fold-tile", (72, 64, 64, 64, False), "f16", {"splits": 36}), ("fold-generic", (260, 32, 32, 8, False), "f16", {"splits": 33}),
+             ("fold-ups", (260, 64, 64, 64, True), "f16", {"splits": 33})]
+    return legs
+
+
+WGRAD_LEGS = _wgrad_legs()
+_WG_CACHE = {}
+
+
+def _wgrad_operands(geo, bn, pre):
+    """Operands of a weight-gradient leg and the fp64 dw of those very operands; computed once per geometry, never modified.
+    -> dict: x, dy (what the launch takes), ref, and for the pre-split legs x_plain / dy_plain (the fp32 tensors the pairs hold,
+    dy_plain carrying the bound its pairs were scaled with)."""
+    key = (geo, bn, pre)
+    if key in _WG_CACHE:
+        return _WG_CACHE[key]
+    h = H()
+    Hh, Ww, C, K, ups = geo
+    hin, win = (Hh // 2, Ww // 2) if ups else (Hh, Ww)
+    o = {}
+    if pre:         # the producer chains of test_presplit_activation_chain (x) and test_presplit_gradient_chain (dy)
+        x0, w0 = nhwc(rnd(2, 64, Hh, Ww, seed=703)), rnd(C, 64, 3, 3, seed=704, scale=(2.0 / (9 * 64)) ** 0.5).to(DEV)
+        y0, st0 = h.conv3x3_fwd(x0, h.conv_weight(w0, "fwd", h.F16X3, x0, C)[0], rnd(C, seed=705, scale=0.1).to(DEV), C, epi=h.EPI_BIAS_STATS,
+                                dtype=h.F16X3, streamed=True, want_bound=True)
+        coef0, am = h.bn_finalize(st0, float(2 * Hh * Ww), (1.0 + 0.3 * rnd(C, seed=706)).to(DEV), (0.2 * rnd(C, seed=707)).to(DEV),
+                                  None, None, 0.1, 1e-5, mm=y0._egz_mm)
+        o["x_plain"] = h.bn_relu_pool_fwd(y0, coef0, False)
+        o["x_pre"] = h.bn_relu_pool_fwd(y0, coef0, False, presplit_am=am)
+        w1 = rnd(K, C, 3, 3, seed=708, scale=(2.0 / (9 * C)) ** 0.5).to(DEV)
+        y1, st1 = h.conv3x3_fwd(o["x_plain"], h.conv_weight(w1, "fwd", h.F16X3, o["x_plain"], K)[0], rnd(K, seed=709, scale=0.1).to(DEV), K,
+                                epi=h.EPI_BIAS_STATS, dtype=h.F16X3, streamed=True, want_bound=True)
+        coef1 = h.bn_finalize(st1, float(2 * Hh * Ww), (1.0 + 0.3 * rnd(K, seed=710)).to(DEV), (0.2 * rnd(K, seed=711)).to(DEV), None, None, 0.1, 1e-5)
+        dout = nhwc(rnd(2, K, Hh, Ww, seed=712, scale=3e-4))
+        o["dy_exact"] = h.bn_relu_pool_bwd(y1, dout, coef1, False)[0]                   # abs-max: the exact one
+        o["dy_pre"] = h.bn_relu_pool_bwd(y1, dout, coef1, False, presplit=(h.absmax_of(dout), y1._egz_mm))[0]
+        o["dy_plain"] = o["dy_exact"].clone()
+        o["dy_plain"]._egz_absmax = o["dy_pre"]._egz_absmax                             # ... the bound the pairs were scaled with
+        assert o["x_pre"]._egz_presplit and o["dy_pre"]._egz_presplit
+        x64, dy64 = nchw(o["x_plain"]).double(), nchw(o["dy_exact"]).double()
+    else:
+        x, dy = rnd(2, C, hin, win, seed=701), rnd(2, K, Hh, Ww, seed=702)
+        o["x"], o["dy"] = nhwc(x), nhwc(dy)
+        x64, dy64 = x.double(), dy.double()
+        if bn:      # x is a pre-BatchNorm tensor: the kernel stages relu(fma(x, scale, shift)), rounded once to fp32; x_absmax = its max
+            coef = torch.stack([0.1 * rnd(C, seed=713), 1.0 + 0.1 * rnd(C, seed=714).abs(), 1.0 + 0.2 * rnd(C, seed=715), 0.1 * rnd(C, seed=716)])
+            xn = torch.addcmul(coef[3].double(), x64.permute(0, 2, 3, 1), coef[2].double()).float().clamp_(min=0)
+            o["coef"] = coef.contiguous().to(DEV)
+            o["x"]._egz_absmax = h.absmax_of(xn.contiguous().to(DEV))      # (xn has the strides of the permuted view)
+            x64 = xn.double().permute(0, 3, 1, 2)
+    xin = F.interpolate(x64, scale_factor=2, mode="nearest") if ups else x64
+    w = torch.zeros(K, C, 3, 3, dtype=torch.float64, requires_grad=True)
+    F.conv2d(xin, w, None, padding=1).backward(dy64)
+    o["ref"] = w.grad
+    _WG_CACHE[key] = o
+    return o
+
+
+@pytest.mark.parametrize("leg", WGRAD_LEGS, ids=[l[0] for l in WGRAD_LEGS])
+def test_wgrad_dispatch_legs(leg, monkeypatch):
+    """Every instantiation egz_conv3x3_wgrad's dispatch can reach, once, at B = 2 and the smallest shape that reaches it: the
+    phase form on split halves, the narrow kernels (nine-tile and tap-packed, with and without the deferred-BatchNorm operand),
+    the 9-tap patch kernel (plain, upsampled, pre-split x / dy / both), the f32 routes (phase form, 9-tap segments, per-tap tiles
+    32 / 64 / 128 and the forced variants) and the three reduce tails behind wgrad_fold_kernel -- against the fp64 weight
+    gradient of F.conv2d at the bars of test_conv3x3_wgrad_split (f32 1e-5, bf16 x3 2e-5, f16 x3 2e-6) and, for two products per
+    MAC, of test_backward_two_products (2e-3 of max |ref| per entry, 1e-3 in relative L2).  A pre-split operand gives the bits of
+    the same launch on the fp32 tensor the pairs hold -- but for x pairs under two products, where x enters rounded from hi + lo
+    in place of the fp32 value (a double rounding apart on rare ties): there the bar of test_presplit_activation_chain, 1e-4."""
+    h = H()
+    name, geo, t, opt = leg
+    Hh, Ww, C, K, ups = geo
+    prec, products = _WG_TYPES[t]
+    monkeypatch.setattr(h, "BWD_PRODUCTS", products)
+    monkeypatch.setattr(h, "WGRAD_TAPPACK", opt.get("tappack", True))
+    monkeypatch.setattr(h, "SPLITK", False)              # (the producer convs of the pre-split legs: as the chain tests)
+    pre = opt.get("pre")
+    o = _wgrad_operands(geo, opt.get("bn", False), bool(pre))
+    flag = getattr(h, opt["flag"]) if "flag" in opt else 0
+    if "splits" in opt:        # more than 32 splits: the size query reports S partials + ceil(S / 32) folded rows
+        S, n = opt["splits"], (16 if ups else 9) * C * K
+        flags = h.WGRAD_SPLIT | (h.WGRAD_UPS if ups else 0)
+        assert S > 32 and int(h.LIB.egz_conv3x3_wgrad_ws_bytes(2, Hh, Ww, C, K, flags)) == (S + (S + 31) // 32) * n * 4
+    if pre:
+        x, dy = (o["x_pre"] if "x" in pre else o["x_plain"]), (o["dy_pre"] if "d" in pre else o["dy_exact"])
+        dw = h.conv3x3_wgrad(x, dy, precision=prec, x_pre="x" in pre, dy_pre="d" in pre)
+        same = h.conv3x3_wgrad(o["x_plain"], o["dy_plain"] if "d" in pre else o["dy_exact"], precision=prec)
+        if "x" in pre and products == 2:
+            print(name, "vs the launch on fp32 operands", rel(dw, same))
+            assert rel(dw, same) < 1e-4
+        else:
+            assert torch.equal(dw, same)
+    else:
+        dw = h.conv3x3_wgrad(o["x"], o["dy"], ups=ups, variant_flag=flag, precision=prec, x_bn=o.get("coef"))
+    err = rel(dw.cpu(), o["ref"])
+    l2 = float((dw.cpu().double() - o["ref"]).norm() / o["ref"].norm())
+    print(name, "rel err", err, "l2", l2)
+    if products == 2:
+        assert err < 2e-3 and l2 < 1e-3
+    else:
+        assert err < _WG_TOL[t]
