@@ -7,7 +7,6 @@
 // second tiny kernel sums them in a fixed order (deterministic, no atomics).
 #include "egz_common.h"
 #include "x3_split.h"
-#include <cstdlib>
 
 namespace {
 
@@ -694,16 +693,84 @@ inline int ew_grid(long n) {
 
 constexpr int BWD_BLOCKS = 1024;
 constexpr int FIN_MAX_ROWS = 512, FIN_GRID = 2048;     // in-kernel finalize: at most this many partial rows / blocks re-summing them
-inline bool fin_in_kernel() { return true; }          // few partial rows: the apply pass sums them itself
+
+// Grid of the reduction passes (bn_bwd_reduce_kernel, relu_bwd_bias_kernel) over `rows` rows of K channels: a thread per channel
+// quad, as many rows per block as 256 threads hold (rpb), one partial row of `cols` fp64 columns per block, staged in dynamic
+// LDS.
+struct RedGrid { int threads, rpb, blocks; size_t shm; };
+inline RedGrid red_grid(long rows, int K, int cols) {
+    const int K4 = K / 4, threads = 256 > K4 ? 256 : K4, rpb = threads / K4;
+    int blocks = (int)((rows + rpb - 1) / rpb);
+    if (blocks > BWD_BLOCKS) blocks = BWD_BLOCKS;
+    if (blocks > ew_cap()) blocks = ew_cap();
+    return {threads, rpb, blocks, (size_t)rpb * cols * sizeof(double)};
+}
+
+// Workspace of such a pass: [BWD_BLOCKS][cols] block partials, then [RED_ROWS][cols] for their fold (fold_rows).
+struct RedWs {
+    double *part, *part2;
+    RedWs(void* ws, int cols) : part(static_cast<double*>(ws)), part2(part + (size_t)BWD_BLOCKS * cols) {}
+    static size_t bytes(int cols) { return ((size_t)BWD_BLOCKS + RED_ROWS) * cols * sizeof(double); }
+};
+// Workspace of the BatchNorm backward, THE definition of its layout (size query and both implementations): the RedWs of the
+// (sum dz, sum dz * xhat) rows (cols = 2 K), then the two per-channel means the finalize step leaves for the apply pass ([K]
+// floats each).  end: the first byte past it, where egz_bn_bwd_first_wgrad appends its weight partials.
+struct BnBwdWs : RedWs {
+    float *mdz, *mdzx, *end;
+    BnBwdWs(void* ws, int K)
+        : RedWs(ws, 2 * K), mdz(reinterpret_cast<float*>(part2 + (size_t)RED_ROWS * 2 * K)), mdzx(mdz + K), end(mdzx + K) {}
+    static size_t bytes(int K) { return RedWs::bytes(2 * K) + 2 * (size_t)K * sizeof(float); }
+};
+
+// At most RED_ROWS partial rows reach the serial per-channel tail of a finalize kernel: more ([n][cols] at src) are column-summed
+// into part2 ([RED_ROWS][cols]) first, and src / n continue from there.
+inline int fold_rows(const double*& src, int& n, double* part2, int cols, hipStream_t st) {
+    if (n <= RED_ROWS) return 0;
+    const int rc = colsum_partial<double>(src, part2, n, cols, st);
+    src = part2;
+    n = RED_ROWS;
+    return rc;
+}
+
+// egz_bn_finalize (who names the entry point in the messages) and, with `bound`, egz_bn_finalize_bound
+int bn_finalize_impl(const char* who, bool bound, const double* stat_partial, int rows, int K, double count, const float* gamma,
+                     const float* beta, float* running_mean, float* running_var, float momentum, float eps, float* mean_out,
+                     float* invstd_out, float* scale, float* shift, long long* num_batches_tracked, void* workspace,
+                     size_t ws_bytes, const unsigned int* minmax, unsigned int* absmax_out, hipStream_t st) {
+    EGZ_CHECK_ARG(stat_partial && mean_out && invstd_out && scale && shift && workspace && (!bound || (minmax && absmax_out)),
+                  "%s: null pointer", who);
+    EGZ_CHECK_ARG(!bound || K % 64 == 0, "%s: K=%d must be a multiple of 64", who, K);
+    EGZ_CHECK_ARG(ws_bytes >= (size_t)RED_ROWS * 2 * K * sizeof(double), "%s: workspace too small", who);
+    EGZ_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "%s: running stats must come in pairs", who);
+    if (int rc = fold_rows(stat_partial, rows, static_cast<double*>(workspace), 2 * K, st)) return rc;
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(egz_cdiv(K, 128)), dim3(128), 0, st, stat_partial, rows, K, count, gamma, beta,
+                       running_mean, running_var, momentum, eps, mean_out, invstd_out, scale, shift, num_batches_tracked,
+                       minmax, absmax_out);
+    EGZ_CHECK_LAUNCH(who);
+    return 0;
+}
+
+// egz_bn_relu_pool_fwd and, with `split` (absmax is then an input), egz_bn_relu_pool_fwd_presplit
+int bn_relu_pool_fwd_impl(const char* who, bool split, const float* y, const float* scale, const float* shift, float* out, int B,
+                          int H, int W, int K, int pool, unsigned int* absmax, hipStream_t st) {
+    EGZ_CHECK_ARG(y && scale && shift && out && (!split || absmax), "%s: null pointer", who);
+    EGZ_CHECK_ARG(K % 4 == 0, "%s: K=%d must be a multiple of 4", who, K);
+    EGZ_CHECK_ARG(!pool || (H % 2 == 0 && W % 2 == 0), "%s: pooled map must be even", who);
+    const long n = (long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (K / 4);
+    resolve([&](auto p, auto s) {
+        hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<decltype(p)::value, decltype(s)::value>), dim3(ew_grid(n)), dim3(256), 0, st,
+                           y, scale, shift, out, B, H, W, K, absmax);
+    }, by_bool(pool), by_bool(split));
+    EGZ_CHECK_LAUNCH(who);
+    return 0;
+}
 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ C ABI
 EGZ_API size_t egz_bn_ws_bytes(int K) {
     // stage-A partials of the forward stats ([RED_ROWS][2][K]) or the backward reduction ([BWD_BLOCKS][2][K])
-    const size_t a = (size_t)RED_ROWS * 2 * K * sizeof(double);
-    const size_t b = (size_t)BWD_BLOCKS * 2 * K * sizeof(double);
-    return a > b ? a : b;
+    return (size_t)(RED_ROWS > BWD_BLOCKS ? RED_ROWS : BWD_BLOCKS) * 2 * K * sizeof(double);
 }
 
 // stat_partial: [rows][2][K] fp64 as written by the conv epilogues.  Produces batch mean / invstd and the fused
@@ -713,23 +780,9 @@ EGZ_API int egz_bn_finalize(const double* stat_partial, int rows, int K, double 
                             const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                             float* mean_out, float* invstd_out, float* scale, float* shift,
                             long long* num_batches_tracked, void* workspace, size_t ws_bytes, hipStream_t st) {
-    EGZ_CHECK_ARG(stat_partial && mean_out && invstd_out && scale && shift && workspace, "egz_bn_finalize: null pointer");
-    EGZ_CHECK_ARG(ws_bytes >= (size_t)RED_ROWS * 2 * K * sizeof(double), "egz_bn_finalize: workspace too small");
-    EGZ_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "egz_bn_finalize: running stats must come in pairs");
-    double* part2 = static_cast<double*>(workspace);
-    const double* src = stat_partial;
-    int nparts = rows;
-    if (rows > RED_ROWS) {
-        int rc = colsum_partial<double>(stat_partial, part2, rows, 2 * K, st);
-        if (rc) return rc;
-        src = part2;
-        nparts = RED_ROWS;
-    }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(egz_cdiv(K, 128)), dim3(128), 0, st, src, nparts, K, count, gamma, beta,
-                       running_mean, running_var, momentum, eps, mean_out, invstd_out, scale, shift, num_batches_tracked,
-                       nullptr, nullptr);
-    EGZ_CHECK_LAUNCH("egz_bn_finalize");
-    return 0;
+    return bn_finalize_impl("egz_bn_finalize", false, stat_partial, rows, K, count, gamma, beta, running_mean, running_var,
+                            momentum, eps, mean_out, invstd_out, scale, shift, num_batches_tracked, workspace, ws_bytes, nullptr,
+                            nullptr, st);
 }
 
 // egz_bn_finalize that also bounds the block output: minmax = the 1024 uints egz_conv3x3_fwd_streamed's minmax_out received on the
@@ -741,25 +794,9 @@ EGZ_API int egz_bn_finalize_bound(const double* stat_partial, int rows, int K, d
                                   float* mean_out, float* invstd_out, float* scale, float* shift,
                                   long long* num_batches_tracked, void* workspace, size_t ws_bytes,
                                   const unsigned int* minmax, unsigned int* absmax_out, hipStream_t st) {
-    EGZ_CHECK_ARG(stat_partial && mean_out && invstd_out && scale && shift && workspace && minmax && absmax_out,
-                  "egz_bn_finalize_bound: null pointer");
-    EGZ_CHECK_ARG(K % 64 == 0, "egz_bn_finalize_bound: K=%d must be a multiple of 64", K);
-    EGZ_CHECK_ARG(ws_bytes >= (size_t)RED_ROWS * 2 * K * sizeof(double), "egz_bn_finalize_bound: workspace too small");
-    EGZ_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "egz_bn_finalize_bound: running stats must come in pairs");
-    double* part2 = static_cast<double*>(workspace);
-    const double* src = stat_partial;
-    int nparts = rows;
-    if (rows > RED_ROWS) {
-        int rc = colsum_partial<double>(stat_partial, part2, rows, 2 * K, st);
-        if (rc) return rc;
-        src = part2;
-        nparts = RED_ROWS;
-    }
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(egz_cdiv(K, 128)), dim3(128), 0, st, src, nparts, K, count, gamma, beta,
-                       running_mean, running_var, momentum, eps, mean_out, invstd_out, scale, shift, num_batches_tracked,
-                       minmax, absmax_out);
-    EGZ_CHECK_LAUNCH("egz_bn_finalize_bound");
-    return 0;
+    return bn_finalize_impl("egz_bn_finalize_bound", true, stat_partial, rows, K, count, gamma, beta, running_mean, running_var,
+                            momentum, eps, mean_out, invstd_out, scale, shift, num_batches_tracked, workspace, ws_bytes, minmax,
+                            absmax_out, st);
 }
 
 // egz_bn_finalize for a BatchNorm whose output is never materialised (the consuming convolution applies it while staging y):
@@ -795,14 +832,7 @@ EGZ_API int egz_bn_eval_coeffs(int K, const float* gamma, const float* beta, con
 // absmax (optional): receives max |out| (egz_absmax layout) -- the f16 x3 scaling of the convolution that consumes `out`.
 EGZ_API int egz_bn_relu_pool_fwd(const float* y, const float* scale, const float* shift, float* out, int B, int H,
                                  int W, int K, int pool, unsigned int* absmax, hipStream_t st) {
-    EGZ_CHECK_ARG(y && scale && shift && out, "egz_bn_relu_pool_fwd: null pointer");
-    EGZ_CHECK_ARG(K % 4 == 0, "egz_bn_relu_pool_fwd: K=%d must be a multiple of 4", K);
-    EGZ_CHECK_ARG(!pool || (H % 2 == 0 && W % 2 == 0), "egz_bn_relu_pool_fwd: pooled map must be even");
-    const long n = (long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (K / 4);
-    if (pool) hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<true>, dim3(ew_grid(n)), dim3(256), 0, st, y, scale, shift, out, B, H, W, K, absmax);
-    else      hipLaunchKernelGGL(bn_relu_pool_fwd_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, st, y, scale, shift, out, B, H, W, K, absmax);
-    EGZ_CHECK_LAUNCH("egz_bn_relu_pool_fwd");
-    return 0;
+    return bn_relu_pool_fwd_impl("egz_bn_relu_pool_fwd", false, y, scale, shift, out, B, H, W, K, pool, absmax, st);
 }
 
 // egz_bn_relu_pool_fwd with the output stored PRE-SPLIT (see bn_relu_pool_fwd_kernel): absmax is an INPUT here, the exact max of
@@ -810,20 +840,11 @@ EGZ_API int egz_bn_relu_pool_fwd(const float* y, const float* scale, const float
 // 0x8000); nothing else can read the tensor.
 EGZ_API int egz_bn_relu_pool_fwd_presplit(const float* y, const float* scale, const float* shift, float* out, int B, int H,
                                           int W, int K, int pool, const unsigned int* absmax, hipStream_t st) {
-    EGZ_CHECK_ARG(y && scale && shift && out && absmax, "egz_bn_relu_pool_fwd_presplit: null pointer");
-    EGZ_CHECK_ARG(K % 4 == 0, "egz_bn_relu_pool_fwd_presplit: K=%d must be a multiple of 4", K);
-    EGZ_CHECK_ARG(!pool || (H % 2 == 0 && W % 2 == 0), "egz_bn_relu_pool_fwd_presplit: pooled map must be even");
-    const long n = (long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W) * (K / 4);
-    unsigned int* am = const_cast<unsigned int*>(absmax);
-    if (pool) hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<true, true>), dim3(ew_grid(n)), dim3(256), 0, st, y, scale, shift, out, B, H, W, K, am);
-    else      hipLaunchKernelGGL((bn_relu_pool_fwd_kernel<false, true>), dim3(ew_grid(n)), dim3(256), 0, st, y, scale, shift, out, B, H, W, K, am);
-    EGZ_CHECK_LAUNCH("egz_bn_relu_pool_fwd_presplit");
-    return 0;
+    return bn_relu_pool_fwd_impl("egz_bn_relu_pool_fwd_presplit", true, y, scale, shift, out, B, H, W, K, pool,
+                                 const_cast<unsigned int*>(absmax), st);
 }
 
-EGZ_API size_t egz_bn_relu_pool_bwd_ws_bytes(int K) {
-    return ((size_t)BWD_BLOCKS + RED_ROWS) * 2 * K * sizeof(double) + 2 * (size_t)K * sizeof(float);
-}
+EGZ_API size_t egz_bn_relu_pool_bwd_ws_bytes(int K) { return BnBwdWs::bytes(K); }
 
 // Backward of [BN(train) -> ReLU -> (pool)] given the saved pre-BN tensor y and the batch statistics.
 // dgamma/dbeta may be null (frozen BN).  dy gets the gradient w.r.t. y ([B][H][W][K]).
@@ -839,61 +860,42 @@ static int bn_relu_pool_bwd_impl(const float* y, const float* dout, const float*
     EGZ_CHECK_ARG(!sums || (sums_rows > 0 && !pool), "egz_bn_relu_pool_bwd: precomputed sums need sums_rows > 0 and no pooling");
     EGZ_CHECK_ARG(K % 4 == 0 && K <= 1024, "egz_bn_relu_pool_bwd: K=%d must be a multiple of 4, <= 1024", K);
     EGZ_CHECK_ARG(!pool || (H % 2 == 0 && W % 2 == 0), "egz_bn_relu_pool_bwd: pooled map must be even");
-    const int K4 = K / 4;
-    const int threads = 256 > K4 ? 256 : K4;
-    const int rpb = threads / K4;
-    const long npix = (long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W);
-    int blocks = (int)((npix + rpb - 1) / rpb);
-    if (blocks > BWD_BLOCKS) blocks = BWD_BLOCKS;
-    if (blocks > ew_cap()) blocks = ew_cap();
-    const size_t need = egz_bn_relu_pool_bwd_ws_bytes(K);
+    const size_t need = BnBwdWs::bytes(K);
     EGZ_CHECK_ARG(ws_bytes >= need, "egz_bn_relu_pool_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
-    double* part = static_cast<double*>(workspace);
-    double* part2 = part + (size_t)BWD_BLOCKS * 2 * K;
-    float* mdz = reinterpret_cast<float*>(part2 + (size_t)RED_ROWS * 2 * K);
-    float* mdzx = mdz + K;
-    const size_t shm = (size_t)rpb * 2 * K * sizeof(double);
-    if (!presplit && sums && sums_rows <= FIN_MAX_ROWS && K <= 64 && 256 % (2 * K) == 0 && fin_in_kernel()) {
-        // few partial rows (persistent narrow kernel): the apply pass sums them itself -- no column-sum / finalize launches
-        const long n = npix * K4;
+    const BnBwdWs ws(workspace, K);
+    const long npix = (long)B * (pool ? H / 2 : H) * (pool ? W / 2 : W), n = npix * (K / 4);
+    const double count = (double)B * H * W;
+    // few partial rows (persistent narrow kernel): the apply pass sums them itself -- no column-sum / finalize launches
+    if (!presplit && sums && sums_rows <= FIN_MAX_ROWS && K <= 64 && 256 % (2 * K) == 0) {
         const int grid = ew_grid(n) < FIN_GRID ? ew_grid(n) : FIN_GRID;
+        const float* none = nullptr;
         hipLaunchKernelGGL((bn_bwd_apply_kernel<false, true>), dim3(grid), dim3(256), 0, st, y, dout, scale, shift, mean, invstd,
-                           (const float*)nullptr, (const float*)nullptr, dy, B, H, W, K, absmax, sums, sums_rows, (double)B * H * W, dgamma, dbeta);
+                           none, none, dy, B, H, W, K, absmax, sums, sums_rows, count, dgamma, dbeta);
         EGZ_CHECK_LAUNCH("egz_bn_relu_pool_bwd(finalize + apply)");
         return 0;
     }
-    if (sums) {
-        part = const_cast<double*>(sums);
-        blocks = sums_rows;
-    } else {
-        if (pool) hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, dim3(blocks), dim3(threads), shm, st, y, dout, scale, shift, mean, invstd, part, B, H, W, K);
-        else      hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(blocks), dim3(threads), shm, st, y, dout, scale, shift, mean, invstd, part, B, H, W, K);
+    const double* fin = sums;
+    int nfin = sums_rows;
+    if (!sums) {
+        const RedGrid g = red_grid(npix, K, 2 * K);
+        resolve([&](auto p) {
+            hipLaunchKernelGGL(bn_bwd_reduce_kernel<decltype(p)::value>, dim3(g.blocks), dim3(g.threads), g.shm, st, y, dout,
+                               scale, shift, mean, invstd, ws.part, B, H, W, K);
+        }, by_bool(pool));
         EGZ_CHECK_LAUNCH("egz_bn_relu_pool_bwd(reduce)");
+        fin = ws.part;
+        nfin = g.blocks;
     }
-    const double* fin = part;
-    int nfin = blocks;
-    if (blocks > RED_ROWS) {            // two-stage: keep the serial per-channel tail at <= RED_ROWS terms
-        int rc = colsum_partial<double>(part, part2, blocks, 2 * K, st);
-        if (rc) return rc;
-        fin = part2;
-        nfin = RED_ROWS;
-    }
-    const long n = npix * K4;
-    if (presplit) {
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(egz_cdiv(K, 64)), dim3(64), 0, st, fin, nfin, K,
-                           (double)B * H * W, dgamma, dbeta, mdz, mdzx, scale, mean, invstd, y_minmax, dout_absmax, absmax);
-        EGZ_CHECK_LAUNCH("egz_bn_relu_pool_bwd_presplit(finalize)");
-        if (pool) hipLaunchKernelGGL((bn_bwd_apply_kernel<true, false, true>), dim3(ew_grid(n)), dim3(256), 0, st, y, dout, scale, shift, mean, invstd, mdz, mdzx, dy, B, H, W, K, absmax);
-        else      hipLaunchKernelGGL((bn_bwd_apply_kernel<false, false, true>), dim3(ew_grid(n)), dim3(256), 0, st, y, dout, scale, shift, mean, invstd, mdz, mdzx, dy, B, H, W, K, absmax);
-        EGZ_CHECK_LAUNCH("egz_bn_relu_pool_bwd_presplit(apply)");
-        return 0;
-    }
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(egz_cdiv(K, 64)), dim3(64), 0, st, fin, nfin, K,
-                       (double)B * H * W, dgamma, dbeta, mdz, mdzx);
-    EGZ_CHECK_LAUNCH("egz_bn_relu_pool_bwd(finalize)");
-    if (pool) hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(n)), dim3(256), 0, st, y, dout, scale, shift, mean, invstd, mdz, mdzx, dy, B, H, W, K, absmax);
-    else      hipLaunchKernelGGL(bn_bwd_apply_kernel<false>, dim3(ew_grid(n)), dim3(256), 0, st, y, dout, scale, shift, mean, invstd, mdz, mdzx, dy, B, H, W, K, absmax);
-    EGZ_CHECK_LAUNCH("egz_bn_relu_pool_bwd(apply)");
+    if (int rc = fold_rows(fin, nfin, ws.part2, 2 * K, st)) return rc;
+    // (the operands past mdzx are read under the bound alone: absmax_out != null)
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(egz_cdiv(K, 64)), dim3(64), 0, st, fin, nfin, K, count, dgamma, dbeta, ws.mdz,
+                       ws.mdzx, scale, mean, invstd, y_minmax, dout_absmax, presplit ? absmax : nullptr);
+    EGZ_CHECK_LAUNCH(presplit ? "egz_bn_relu_pool_bwd_presplit(finalize)" : "egz_bn_relu_pool_bwd(finalize)");
+    resolve([&](auto p, auto s) {
+        hipLaunchKernelGGL((bn_bwd_apply_kernel<decltype(p)::value, false, decltype(s)::value>), dim3(ew_grid(n)), dim3(256), 0,
+                           st, y, dout, scale, shift, mean, invstd, ws.mdz, ws.mdzx, dy, B, H, W, K, absmax);
+    }, by_bool(pool), by_bool(presplit));
+    EGZ_CHECK_LAUNCH(presplit ? "egz_bn_relu_pool_bwd_presplit(apply)" : "egz_bn_relu_pool_bwd(apply)");
     return 0;
 }
 
@@ -1058,7 +1060,7 @@ __global__ __launch_bounds__(256) void first_wgrad_rows_kernel(const float* __re
 }  // namespace
 
 EGZ_API size_t egz_bn_bwd_first_wgrad_ws_bytes(int C, int K) {
-    return egz_bn_relu_pool_bwd_ws_bytes(K) + (size_t)FWG_BLOCKS * K * C * 9 * sizeof(float);
+    return BnBwdWs::bytes(K) + (size_t)FWG_BLOCKS * K * C * 9 * sizeof(float);
 }
 
 // Backward of the FIRST block [Conv2d(C -> 32, 3x3) -> BN(train) -> ReLU] of a narrow stack (late_fusion.py:10-12; C <= 3):
@@ -1075,35 +1077,25 @@ EGZ_API int egz_bn_bwd_first_wgrad(const float* y, const float* dout, const floa
     EGZ_CHECK_ARG(!sums || sums_rows > 0, "egz_bn_bwd_first_wgrad: sums need sums_rows > 0");
     const size_t need = egz_bn_bwd_first_wgrad_ws_bytes(C, K);
     EGZ_CHECK_ARG(ws_bytes >= need, "egz_bn_bwd_first_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
-    const int K4 = K / 4, threads = 256, rpb = threads / K4;
+    const BnBwdWs ws(workspace, K);
+    float* wpart = ws.end;
     const long npix = (long)B * H * W;
-    int blocks = (int)((npix + rpb - 1) / rpb);
-    if (blocks > BWD_BLOCKS) blocks = BWD_BLOCKS;
-    if (blocks > ew_cap()) blocks = ew_cap();
-    double* part = static_cast<double*>(workspace);
-    double* part2 = part + (size_t)BWD_BLOCKS * 2 * K;
-    float* mdz = reinterpret_cast<float*>(part2 + (size_t)RED_ROWS * 2 * K);
-    float* mdzx = mdz + K;
-    float* wpart = reinterpret_cast<float*>(static_cast<char*>(workspace) + egz_bn_relu_pool_bwd_ws_bytes(K));
-    const bool fin_fused = sums && sums_rows <= FIN_MAX_ROWS && K <= 64 && fin_in_kernel();
-    if (sums) {
-        part = const_cast<double*>(sums);
-        blocks = sums_rows;
-    } else {
-        hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(blocks), dim3(threads), (size_t)rpb * 2 * K * sizeof(double), st, y, dout,
-                           scale, shift, mean, invstd, part, B, H, W, K);
+    // few partial rows: the kernel sums them itself (bn_bwd_finalize_in_block), as in egz_bn_relu_pool_bwd
+    const bool fin_fused = sums && sums_rows <= FIN_MAX_ROWS && K <= 64;
+    const double* fin = sums;
+    int nfin = sums_rows;
+    if (!sums) {
+        const RedGrid g = red_grid(npix, K, 2 * K);
+        hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, dim3(g.blocks), dim3(g.threads), g.shm, st, y, dout, scale, shift, mean,
+                           invstd, ws.part, B, H, W, K);
         EGZ_CHECK_LAUNCH("egz_bn_bwd_first_wgrad(reduce)");
+        fin = ws.part;
+        nfin = g.blocks;
     }
     if (!fin_fused) {
-        const double* fin = part;
-        int nfin = blocks;
-        if (blocks > RED_ROWS) {
-            int rc = colsum_partial<double>(part, part2, blocks, 2 * K, st);
-            if (rc) return rc;
-            fin = part2;
-            nfin = RED_ROWS;
-        }
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(egz_cdiv(K, 64)), dim3(64), 0, st, fin, nfin, K, (double)npix, dgamma, dbeta, mdz, mdzx);
+        if (int rc = fold_rows(fin, nfin, ws.part2, 2 * K, st)) return rc;
+        hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(egz_cdiv(K, 64)), dim3(64), 0, st, fin, nfin, K, (double)npix, dgamma,
+                           dbeta, ws.mdz, ws.mdzx);
         EGZ_CHECK_LAUNCH("egz_bn_bwd_first_wgrad(finalize)");
     }
     // pixels per thread: 4 (W % 4 == 0; C = 3: 2 -- with 108 accumulators the 4-pixel form is left with one wave per SIMD) or 1
@@ -1112,32 +1104,16 @@ EGZ_API int egz_bn_bwd_first_wgrad(const float* y, const float* dout, const floa
     int ppb = (int)((npix + FWG_BLOCKS - 1) / FWG_BLOCKS);
     ppb = (ppb + step - 1) / step * step;
     const int nb = (int)((npix + ppb - 1) / ppb);
-#define EGZ_FWG3(CC, PP, QQ)                                                                                                     \
-    do {                                                                                                                         \
-        if (fin_fused)                                                                                                           \
-            hipLaunchKernelGGL((bn_bwd_first_wgrad_kernel<CC, PP, true, QQ>), dim3(nb), dim3(256), 0, st, y, dout, scale, shift, mean, invstd, \
-                               (const float*)nullptr, (const float*)nullptr, x, wpart, B, H, W, ppb, sums, sums_rows, (double)npix, dgamma, dbeta); \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((bn_bwd_first_wgrad_kernel<CC, PP, false, QQ>), dim3(nb), dim3(256), 0, st, y, dout, scale, shift, mean, invstd, \
-                               mdz, mdzx, x, wpart, B, H, W, ppb, (const double*)nullptr, 0, 1.0, (float*)nullptr, (float*)nullptr); \
-    } while (0)
-#define EGZ_FWG2(CC, PP)                                                                                                         \
-    do {                                                                                                                         \
-        if (K == 32) EGZ_FWG3(CC, PP, 8);                                                                                        \
-        else EGZ_FWG3(CC, PP, 16);                                                                                               \
-    } while (0)
-#define EGZ_FWG(CC)                                                                                                              \
-    do {                                                                                                                         \
-        if (pxt == 4) EGZ_FWG2(CC, 4);                                                                                           \
-        else EGZ_FWG2(CC, 1);                                                                                                    \
-    } while (0)
-    if (C == 1) EGZ_FWG(1);
-    else if (C == 2) EGZ_FWG(2);
-    else if (pxt == 2) EGZ_FWG2(3, 2);
-    else EGZ_FWG2(3, 1);
-#undef EGZ_FWG
-#undef EGZ_FWG2
-#undef EGZ_FWG3
+    // what the finalize step hands the kernel: partial rows to sum in the block, or the means bn_bwd_finalize_kernel left
+    struct Fin { const float *mdz, *mdzx; const double* rows; int nrows; double count; float *dgamma, *dbeta; };
+    const Fin f = fin_fused ? Fin{nullptr, nullptr, sums, sums_rows, (double)npix, dgamma, dbeta}
+                            : Fin{ws.mdz, ws.mdzx, nullptr, 0, 1.0, nullptr, nullptr};
+    resolve([&](auto c, auto wide, auto fk, auto q) {
+        constexpr int CIN = decltype(c)::value, PX = !decltype(wide)::value ? 1 : CIN == 3 ? 2 : 4, KQ = decltype(q)::value;
+        hipLaunchKernelGGL((bn_bwd_first_wgrad_kernel<CIN, PX, decltype(fk)::value, KQ>), dim3(nb), dim3(256), 0, st, y, dout,
+                           scale, shift, mean, invstd, f.mdz, f.mdzx, x, wpart, B, H, W, ppb, f.rows, f.nrows, f.count, f.dgamma,
+                           f.dbeta);
+    }, by_int<1, 2, 3>(C), by_bool(pxt > 1), by_bool(fin_fused), by_int<8, 16>(K / 4));
     EGZ_CHECK_LAUNCH("egz_bn_bwd_first_wgrad(apply + wgrad)");
     const int n = K * C * 9;
     hipLaunchKernelGGL(first_wgrad_rows_kernel, dim3(egz_cdiv(n, 16)), dim3(256), 0, st, wpart, dw, nb, n);
@@ -1172,9 +1148,6 @@ EGZ_API int egz_absmax(const float* x, long n, unsigned int* absmax, hipStream_t
     return 0;
 }
 
-// per-channel sum / sum-of-squares partials of an NHWC tensor [rows][K] in the conv-epilogue format, so that
-// egz_bn_finalize can consume them: stat_partial must hold RED_ROWS*2*K doubles.
-EGZ_API int egz_channel_stats(const float* x, long rows, int K, double* stat_partial, hipStream_t st);
 EGZ_API int egz_channel_stats_rows(void) { return RED_ROWS; }
 
 namespace {
@@ -1204,6 +1177,8 @@ __global__ __launch_bounds__(256) void channel_stats_kernel(const float* __restr
 }
 }  // namespace
 
+// per-channel sum / sum-of-squares partials of an NHWC tensor [rows][K] in the conv-epilogue format, so that
+// egz_bn_finalize can consume them: stat_partial must hold RED_ROWS*2*K doubles.
 EGZ_API int egz_channel_stats(const float* x, long rows, int K, double* stat_partial, hipStream_t st) {
     EGZ_CHECK_ARG(x && stat_partial && rows > 0 && K > 0, "egz_channel_stats: bad arguments");
     hipLaunchKernelGGL(channel_stats_kernel, dim3(egz_cdiv(K, 32), RED_ROWS), dim3(256), 0, st, x, stat_partial, rows, K);
@@ -1218,7 +1193,7 @@ EGZ_API int egz_relu_bwd(const float* out, const float* dout, float* dy, long n,
     return 0;
 }
 
-EGZ_API size_t egz_relu_bwd_bias_ws_bytes(int K) { return ((size_t)BWD_BLOCKS + RED_ROWS) * K * sizeof(double); }
+EGZ_API size_t egz_relu_bwd_bias_ws_bytes(int K) { return RedWs::bytes(K); }
 
 // ReLU backward fused with the bias gradient of the conv that produced `out`: dy = dout*(out>0), db[k] = sum_rows dy.
 EGZ_API int egz_relu_bwd_bias(const float* out, const float* dout, float* dy, float* db, long rows, int K,
@@ -1226,25 +1201,13 @@ EGZ_API int egz_relu_bwd_bias(const float* out, const float* dout, float* dy, fl
     EGZ_CHECK_ARG(out && dout && dy && db && workspace, "egz_relu_bwd_bias: null pointer");
     EGZ_CHECK_ARG(K % 4 == 0 && K <= 1024, "egz_relu_bwd_bias: K=%d must be a multiple of 4, <= 1024", K);
     EGZ_CHECK_ARG(ws_bytes >= egz_relu_bwd_bias_ws_bytes(K), "egz_relu_bwd_bias: workspace too small");
-    const int K4 = K / 4;
-    const int threads = 256 > K4 ? 256 : K4;
-    const int rpb = threads / K4;
-    int blocks = (int)((rows + rpb - 1) / rpb);
-    if (blocks > BWD_BLOCKS) blocks = BWD_BLOCKS;
-    if (blocks > ew_cap()) blocks = ew_cap();
-    double* part = static_cast<double*>(workspace);
-    double* part2 = part + (size_t)BWD_BLOCKS * K;
-    hipLaunchKernelGGL(relu_bwd_bias_kernel, dim3(blocks), dim3(threads), (size_t)rpb * K * sizeof(double), st, out,
-                       dout, dy, part, rows, K, absmax);
+    const RedGrid g = red_grid(rows, K, K);
+    const RedWs ws(workspace, K);
+    hipLaunchKernelGGL(relu_bwd_bias_kernel, dim3(g.blocks), dim3(g.threads), g.shm, st, out, dout, dy, ws.part, rows, K, absmax);
     EGZ_CHECK_LAUNCH("egz_relu_bwd_bias");
-    const double* fin = part;
-    int nfin = blocks;
-    if (blocks > RED_ROWS) {
-        int rc = colsum_partial<double>(part, part2, blocks, K, st);
-        if (rc) return rc;
-        fin = part2;
-        nfin = RED_ROWS;
-    }
+    const double* fin = ws.part;
+    int nfin = g.blocks;
+    if (int rc = fold_rows(fin, nfin, ws.part2, K, st)) return rc;
     hipLaunchKernelGGL(colsum_final_kernel, dim3(egz_cdiv(K, 64)), dim3(64), 0, st, fin, nfin, K, db);
     EGZ_CHECK_LAUNCH("egz_relu_bwd_bias(final)");
     return 0;
@@ -1356,16 +1319,8 @@ EGZ_API int egz_colsum_f64(const double* part, int rows, int cols, int ncols_out
                            size_t ws_bytes, hipStream_t st) {
     EGZ_CHECK_ARG(part && out && workspace && rows > 0 && cols > 0 && ncols_out > 0 && ncols_out <= cols, "egz_colsum_f64: bad arguments");
     EGZ_CHECK_ARG(ws_bytes >= (size_t)RED_ROWS * cols * sizeof(double), "egz_colsum_f64: workspace too small");
-    const double* src = part;
-    int n = rows;
-    if (rows > RED_ROWS) {
-        double* part2 = static_cast<double*>(workspace);
-        int rc = colsum_partial<double>(part, part2, rows, cols, st);
-        if (rc) return rc;
-        src = part2;
-        n = RED_ROWS;
-    }
-    hipLaunchKernelGGL(colsum_final_n_kernel, dim3(egz_cdiv(ncols_out, 128)), dim3(128), 0, st, src, n, cols, ncols_out, out);
+    if (int rc = fold_rows(part, rows, static_cast<double*>(workspace), cols, st)) return rc;
+    hipLaunchKernelGGL(colsum_final_n_kernel, dim3(egz_cdiv(ncols_out, 128)), dim3(128), 0, st, part, rows, cols, ncols_out, out);
     EGZ_CHECK_LAUNCH("egz_colsum_f64");
     return 0;
 }

@@ -1273,9 +1273,6 @@ struct ConvArgs {
     const unsigned int* a_absmax; const float* mask_src; unsigned int* absmax_out; const float* bn_coef; float* minmax;
     hipStream_t st;
 };
-// run-time value -> template argument: a launcher picks the tag and hands it to a generic lambda
-template <int V> using Int = std::integral_constant<int, V>;
-template <typename T> struct TypeTag { using type = T; };
 
 template <typename T>
 int launch_x3p_narrow(int epi, const ConvArgs& a) {

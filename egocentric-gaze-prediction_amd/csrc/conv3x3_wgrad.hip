@@ -1686,15 +1686,8 @@ void wgrad_launch(Kern kern, const WgradArgs& a, const WgradPlan& p, Tail... tai
     hipLaunchKernelGGL(kern, p.grid, dim3(256), 0, a.st, a.x, a.dy, a.part, a.B, a.H, a.W, a.C, a.K, p.per, tail...);
 }
 
-// run-time value -> template argument: a resolver picks the tag and hands it on; resolve(go, r1, r2, ...) calls go(tag1, tag2, ...)
-template <int V> using Int = std::integral_constant<int, V>;
-template <typename T> struct TypeTag { using type = T; };
+// the resolvers of this file (Int, TypeTag, resolve, by_bool: egz_common.h)
 template <int R_, int WD_> struct Patch { static constexpr int R = R_, WD = WD_; };
-template <typename F> void resolve(F&& go) { go(); }
-template <typename F, typename R, typename... Rs> void resolve(F&& go, R&& r, Rs&&... rs) {
-    r([&](auto tag) { resolve([&](auto... rest) { go(tag, rest...); }, rs...); });
-}
-auto by_bool(bool b) { return [b](auto&& k) { if (b) k(std::true_type{}); else k(std::false_type{}); }; }
 // operand type of the split-half kernels: bf16 x3 without dy_absmax, f16 x3 with it, two products per MAC under WG_P2
 auto by_type(const WgradArgs& a, int flags) {
     return [f16 = a.dy_absmax != nullptr, p2 = (flags & WG_P2) != 0](auto&& k) {

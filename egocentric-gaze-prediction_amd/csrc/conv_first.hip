@@ -410,38 +410,19 @@ EGZ_API int egz_conv_first_fwd(const float* x, const float* w, const float* bias
     const long M = (long)B * H * W;
     if (first_direct_ok(C, K) && M * K < (1l << 31)) {
         const int ppb = first_direct_ppb(M, W, K), nb = egz_cdiv(M, ppb);
-#define EGZ_FD3(CC, PP, QQ)                                                                                                    \
-    do {                                                                                                                       \
-        if (stat_partial) hipLaunchKernelGGL((conv_first_direct_kernel<CC, PP, true, QQ>), dim3(nb), dim3(256), 0, st, x, w, bias, y, stat_partial, B, H, W, ppb, minmax_out, minmax_ordered); \
-        else              hipLaunchKernelGGL((conv_first_direct_kernel<CC, PP, false, QQ>), dim3(nb), dim3(256), 0, st, x, w, bias, y, stat_partial, B, H, W, ppb, (float*)nullptr, (unsigned int*)nullptr); \
-    } while (0)
-#define EGZ_FD2(CC, PP)                                                                                                        \
-    do {                                                                                                                       \
-        if (K == 32) EGZ_FD3(CC, PP, 8);                                                                                       \
-        else EGZ_FD3(CC, PP, 16);                                                                                              \
-    } while (0)
-#define EGZ_FD(CC)                                                                                                             \
-    do {                                                                                                                       \
-        if (W % 4 == 0) EGZ_FD2(CC, 4);                                                                                        \
-        else EGZ_FD2(CC, 1);                                                                                                   \
-    } while (0)
-        if (C == 1) EGZ_FD(1);
-        else if (C == 2) EGZ_FD(2);
-        else EGZ_FD(3);
-#undef EGZ_FD
-#undef EGZ_FD2
-#undef EGZ_FD3
+        // (minmax_out / minmax_ordered are null without stat_partial: the guard above)
+        resolve([&](auto c, auto wide, auto s, auto q) {
+            constexpr int CIN = decltype(c)::value, PX = decltype(wide)::value ? 4 : 1, KQ = decltype(q)::value;
+            hipLaunchKernelGGL((conv_first_direct_kernel<CIN, PX, decltype(s)::value, KQ>), dim3(nb), dim3(256), 0, st, x, w, bias,
+                               y, stat_partial, B, H, W, ppb, minmax_out, minmax_ordered);
+        }, by_int<1, 2, 3>(C), by_bool(W % 4 == 0), by_bool(stat_partial != nullptr), by_int<8, 16>(K / 4));
         EGZ_CHECK_LAUNCH("egz_conv_first_fwd(direct)");
         return 0;
     }
-    const int grid = egz_cdiv((long)B * H * W, FM);
-    if (K == 64) {
-        if (stat_partial) hipLaunchKernelGGL((conv_first_fwd_kernel<true, 2>), dim3(grid), dim3(256), 0, st, x, w, bias, y, stat_partial, B, H, W, C);
-        else              hipLaunchKernelGGL((conv_first_fwd_kernel<false, 2>), dim3(grid), dim3(256), 0, st, x, w, bias, y, stat_partial, B, H, W, C);
-    } else {
-        if (stat_partial) hipLaunchKernelGGL((conv_first_fwd_kernel<true, 1>), dim3(grid), dim3(256), 0, st, x, w, bias, y, stat_partial, B, H, W, C);
-        else              hipLaunchKernelGGL((conv_first_fwd_kernel<false, 1>), dim3(grid), dim3(256), 0, st, x, w, bias, y, stat_partial, B, H, W, C);
-    }
+    resolve([&](auto s, auto kt) {
+        hipLaunchKernelGGL((conv_first_fwd_kernel<decltype(s)::value, decltype(kt)::value>), dim3(egz_cdiv(M, FM)), dim3(256), 0,
+                           st, x, w, bias, y, stat_partial, B, H, W, C);
+    }, by_bool(stat_partial != nullptr), by_int<2, 1>(K / 32));
     EGZ_CHECK_LAUNCH("egz_conv_first_fwd");
     return 0;
 }
@@ -465,13 +446,10 @@ EGZ_API int egz_conv_first_wgrad(const float* x, const float* dy, float* dw, int
     long pps = (M + S - 1) / S;
     pps = (pps + 127) / 128 * 128;
     float* part = static_cast<float*>(workspace);
-    if (K == 64) {
-        if (KP == 32) hipLaunchKernelGGL((conv_first_wgrad_kernel<1, 2>), dim3(S), dim3(256), 0, st, x, dy, part, B, H, W, C, pps);
-        else          hipLaunchKernelGGL((conv_first_wgrad_kernel<6, 2>), dim3(S), dim3(256), 0, st, x, dy, part, B, H, W, C, pps);
-    } else {
-        if (KP == 32) hipLaunchKernelGGL((conv_first_wgrad_kernel<1, 1>), dim3(S), dim3(256), 0, st, x, dy, part, B, H, W, C, pps);
-        else          hipLaunchKernelGGL((conv_first_wgrad_kernel<6, 1>), dim3(S), dim3(256), 0, st, x, dy, part, B, H, W, C, pps);
-    }
+    resolve([&](auto nt, auto kt) {
+        hipLaunchKernelGGL((conv_first_wgrad_kernel<decltype(nt)::value, decltype(kt)::value>), dim3(S), dim3(256), 0, st, x, dy,
+                           part, B, H, W, C, pps);
+    }, by_int<1, 6>(KP / 32), by_int<2, 1>(K / 32));
     EGZ_CHECK_LAUNCH("egz_conv_first_wgrad");
     hipLaunchKernelGGL(first_wgrad_reduce_kernel, dim3(egz_cdiv(K * 9 * C, 32)), dim3(256), 0, st, part, dw, K, 9 * C, KP, S * NPG);
     EGZ_CHECK_LAUNCH("egz_conv_first_wgrad(reduce)");

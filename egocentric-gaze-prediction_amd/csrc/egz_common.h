@@ -4,6 +4,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #define EGZ_API extern "C" __attribute__((visibility("default")))
 
@@ -42,6 +43,25 @@ template <typename T> struct egz_drop_alo { static constexpr bool value = false;
 template <> struct egz_drop_alo<egz_f16p2> { static constexpr bool value = true; };
 
 static inline int egz_cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// Run-time value -> template argument (host side).  A resolver (by_bool, or a launcher's own by_...) picks a tag type and hands
+// it on; resolve(go, r1, r2, ...) calls go(tag1, tag2, ...), a generic lambda that names the instantiation and launches it.
+template <int V> using Int = std::integral_constant<int, V>;
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> void resolve(F&& go) { go(); }
+template <typename F, typename R, typename... Rs> void resolve(F&& go, R&& r, Rs&&... rs) {
+    r([&](auto tag) { resolve([&](auto... rest) { go(tag, rest...); }, rs...); });
+}
+// by_int<A, B, ...>(v): Int<A> if v == A, else Int<B> if v == B, ...; the last of the list takes what matched none (the entry
+// point's guards have narrowed v to the list by then)
+template <int V0, int... Vs> auto by_int(int v) {
+    return [v](auto&& k) {
+        if constexpr (sizeof...(Vs) == 0) k(Int<V0>{});
+        else if (v == V0) k(Int<V0>{});
+        else by_int<Vs...>(v)(k);
+    };
+}
+inline auto by_bool(bool b) { return [b](auto&& k) { if (b) k(std::true_type{}); else k(std::false_type{}); }; }
 
 // 32x32 accumulator element `reg` of lane `lane` sits at row (reg&3)+8*(reg>>2)+4*(lane>>5),
 // column lane&31 (cdna_hip_programming.md section 3; dtype-independent on gfx950).

@@ -984,17 +984,14 @@ def bn_finalize(stat: torch.Tensor, count: float, gamma, beta, running_mean, run
     ws = workspace(LIB.egz_bn_ws_bytes(K), dev)
     if running_mean is not None:        # written behind torch's back: invalidate what is cached on it (bn_eval_coeffs)
         running_mean._egz_epoch = getattr(running_mean, "_egz_epoch", 0) + 1
+    args = (stat.data_ptr(), rows, K, float(count), _p(gamma), _p(beta), _p(running_mean), _p(running_var), momentum, eps,
+            coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), _p(num_batches_tracked),
+            ws.data_ptr(), ws.numel())
     if mm is not None:
         am = _new_absmax(dev)
-        check(LIB.egz_bn_finalize_bound(stat.data_ptr(), rows, K, float(count), _p(gamma), _p(beta), _p(running_mean),
-                                        _p(running_var), momentum, eps, coef[0].data_ptr(), coef[1].data_ptr(),
-                                        coef[2].data_ptr(), coef[3].data_ptr(), _p(num_batches_tracked), ws.data_ptr(),
-                                        ws.numel(), mm.data_ptr(), am.data_ptr(), _stream()), "egz_bn_finalize_bound")
+        check(LIB.egz_bn_finalize_bound(*args, mm.data_ptr(), am.data_ptr(), _stream()), "egz_bn_finalize_bound")
         return coef, am
-    check(LIB.egz_bn_finalize(stat.data_ptr(), rows, K, float(count), _p(gamma), _p(beta), _p(running_mean),
-                              _p(running_var), momentum, eps, coef[0].data_ptr(), coef[1].data_ptr(),
-                              coef[2].data_ptr(), coef[3].data_ptr(), _p(num_batches_tracked), ws.data_ptr(), ws.numel(),
-                              _stream()), "egz_bn_finalize")
+    check(LIB.egz_bn_finalize(*args, _stream()), "egz_bn_finalize")
     return coef
 
 
@@ -1124,16 +1121,15 @@ def bn_relu_pool_fwd(y: torch.Tensor, coef: torch.Tensor, pool: bool, out: Optio
     _req(y, "y")
     B, H, W, K = y.shape
     out = _out(out, (B, H // 2, W // 2, K) if pool else (B, H, W, K), y.device)
+    args = (y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), out.data_ptr(), B, H, W, K, int(pool))
     if presplit_am is not None:
-        check(LIB.egz_bn_relu_pool_fwd_presplit(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), out.data_ptr(), B, H, W, K,
-                                                int(pool), presplit_am.data_ptr(), _stream()), "egz_bn_relu_pool_fwd_presplit")
+        check(LIB.egz_bn_relu_pool_fwd_presplit(*args, presplit_am.data_ptr(), _stream()), "egz_bn_relu_pool_fwd_presplit")
         out._egz_absmax = presplit_am
         out._egz_presplit = True
         PRESPLIT_STATS["produced"] += 1
         return out
     am = _new_absmax(y.device) if _want_fwd_absmax() else None
-    check(LIB.egz_bn_relu_pool_fwd(y.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), out.data_ptr(), B, H, W, K,
-                                   int(pool), _p(am), _stream()), "egz_bn_relu_pool_fwd")
+    check(LIB.egz_bn_relu_pool_fwd(*args, _p(am), _stream()), "egz_bn_relu_pool_fwd")
     if am is not None:
         out._egz_absmax = am      # max |out|, folded into the same pass: scales the f16 split of the consuming convolution
     return out
@@ -1151,25 +1147,18 @@ def bn_relu_pool_bwd(y: torch.Tensor, dout: torch.Tensor, coef: torch.Tensor, po
     dy = torch.empty_like(y)
     dg, db = _out(out_dgamma, (K,), y.device), _out(out_dbeta, (K,), y.device)
     ws = workspace(LIB.egz_bn_relu_pool_bwd_ws_bytes(K), y.device)
+    am = _new_absmax(y.device) if presplit is not None or _want_absmax() else None
+    args = (y.data_ptr(), dout.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), coef[0].data_ptr(), coef[1].data_ptr(),
+            dy.data_ptr(), dg.data_ptr(), db.data_ptr(), B, H, W, K, int(pool), ws.data_ptr(), ws.numel(), _p(am), _p(sums),
+            0 if sums is None else sums.shape[0])
     if presplit is not None:
         dout_am, y_mm = presplit
-        am = _new_absmax(y.device)
-        check(LIB.egz_bn_relu_pool_bwd_presplit(y.data_ptr(), dout.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(),
-                                                coef[0].data_ptr(), coef[1].data_ptr(), dy.data_ptr(), dg.data_ptr(),
-                                                db.data_ptr(), B, H, W, K, int(pool), ws.data_ptr(), ws.numel(), am.data_ptr(),
-                                                _p(sums), 0 if sums is None else sums.shape[0], y_mm.data_ptr(),
-                                                dout_am.data_ptr(), _stream()), "egz_bn_relu_pool_bwd_presplit")
-        if sums is not None:
-            BNSUMS_STATS["consumed"] += 1
-        dy._egz_absmax = am
+        check(LIB.egz_bn_relu_pool_bwd_presplit(*args, y_mm.data_ptr(), dout_am.data_ptr(), _stream()),
+              "egz_bn_relu_pool_bwd_presplit")
         dy._egz_presplit = True
         PRESPLIT_STATS["grad_produced"] += 1
-        return dy, dg, db
-    am = _new_absmax(y.device) if _want_absmax() else None
-    check(LIB.egz_bn_relu_pool_bwd(y.data_ptr(), dout.data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(),
-                                   coef[0].data_ptr(), coef[1].data_ptr(), dy.data_ptr(), dg.data_ptr(),
-                                   db.data_ptr(), B, H, W, K, int(pool), ws.data_ptr(), ws.numel(), _p(am),
-                                   _p(sums), 0 if sums is None else sums.shape[0], _stream()), "egz_bn_relu_pool_bwd")
+    else:
+        check(LIB.egz_bn_relu_pool_bwd(*args, _stream()), "egz_bn_relu_pool_bwd")
     if sums is not None:
         BNSUMS_STATS["consumed"] += 1
     if am is not None:

@@ -1477,3 +1477,236 @@ def test_wgrad_dispatch_legs(leg, monkeypatch):
         assert err < 2e-3 and l2 < 1e-3
     else:
         assert err < _WG_TOL[t]
+
+
+# ---- dispatch legs of the BatchNorm passes (csrc/bn_pool.hip) and of the first-layer convolution (csrc/conv_first.hip)
+_BF_W = (16, 18, 13)           # W % 4 == 0: 4 pixels per thread (Cin 1, 2); even: 2 (Cin 3); odd: 1
+_BF_CACHE = {}
+
+
+def _bf_legs():
+    legs = []
+    for C in (1, 2, 3):
+        for K in (32, 64):
+            for W in _BF_W:
+                legs += [(f"fwg-c{C}-w{W}-k{K}-{s}", "fwg", (2, 9 + W % 8, W, C, K, s)) for s in ("nosums", "sums3", "sums520")]
+            legs.append((f"fwg-c{C}-48x48-k{K}-nosums", "fwg", (1, 48, 48, C, K, "nosums")))     # the reduce pass writes > RED_ROWS rows
+    for K in (8, 12, 64, 512):         # 12: 256 % (2 K) != 0, no fused apply; 512: two rows per block of the reduce pass
+        legs += [(f"bwd-k{K}-{'pool' if p else 'nopool'}-nosums", "bwd", (K, p, "nosums")) for p in (False, True)]
+        legs += [(f"bwd-k{K}-nopool-{s}", "bwd", (K, False, s)) for s in ("sums3", "sums520")]
+    legs += [(f"bwd-presplit-{'pool' if p else 'nopool'}", "bwd_pre", (p,)) for p in (False, True)]
+    legs += [(f"fwd-presplit-{'pool' if p else 'nopool'}", "fwd", (p,)) for p in (False, True)]
+    legs += [(f"finalize-{'bound' if mm else 'plain'}-rows{r}", "fin", (mm, r)) for mm in (False, True) for r in (3, 70)]
+    for C in (1, 2, 3):
+        legs += [(f"first-c{C}-w{W}-k{K}-{'stats' if s else 'plain'}", "first", (2, 9 + W % 8, W, C, K, s))
+                 for W in (16, 13) for K in (32, 64) for s in (True, False)]
+    legs += [(f"first-c20-k{K}-{'stats' if s else 'plain'}", "first", (2, 12, 16, 20, K, s)) for K in (32, 64) for s in (True, False)]
+    legs += [(f"first-wgrad-c{C}-k{K}", "first_wgrad", (2, 12, 16, C, K)) for C in (3, 20) for K in (32, 64)]
+    return legs
+
+
+BN_FIRST_LEGS = _bf_legs()
+
+
+def _bf_sums(dz, xhat, rows):
+    """(rows, 2, K) fp64 partial rows of (sum dz, sum dz * xhat) over [pixels][K] operands: three thirds of the pixels, the
+    other rows (if any) zero."""
+    K = dz.shape[1]
+    s = torch.zeros(rows, 2, K, dtype=torch.float64)
+    for r, idx in zip((0, rows // 2, rows - 1), torch.tensor_split(torch.arange(dz.shape[0]), 3)):
+        s[r, 0], s[r, 1] = dz[idx].sum(0), (dz[idx] * xhat[idx]).sum(0)
+    return s.to(DEV)
+
+
+def _bf_block(key, y, gamma, beta, pool, dout_seed):
+    """fp64 autograd of BatchNorm2d(train) -> ReLU (-> MaxPool2d(2, 2)) on y (B, K, H, W): the fp32 coefficient rows the kernels
+    take, the output, dout and the three gradients; with the (dz, xhat) pixel rows the partial sums are made of.  Cached."""
+    if key in _BF_CACHE:
+        return _BF_CACHE[key]
+    y64 = y.double().requires_grad_(True)
+    g64, b64 = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
+    act = F.relu(F.batch_norm(y64, None, None, g64, b64, training=True, eps=1e-5))
+    out = F.max_pool2d(act, 2, 2) if pool else act
+    dout = rnd(*out.shape, seed=dout_seed)
+    out.backward(dout.double())
+    yd = y64.detach()
+    mean, invstd = yd.mean((0, 2, 3)), 1.0 / torch.sqrt(yd.var((0, 2, 3), unbiased=False) + 1e-5)
+    coef64 = torch.stack([mean, invstd, gamma.double() * invstd, beta.double() - mean * gamma.double() * invstd])
+    K = y.shape[1]
+    r = {"coef64": coef64, "coef": coef64.float().to(DEV), "out": out.detach(), "dout": dout, "dy": y64.grad, "dg": g64.grad,
+         "db": b64.grad, "yd": nhwc(y), "dd": nhwc(dout)}
+    if not pool:
+        r["dz"] = (dout.double() * (act.detach() > 0)).permute(0, 2, 3, 1).reshape(-1, K)
+        r["xhat"] = ((yd - mean.view(1, -1, 1, 1)) * invstd.view(1, -1, 1, 1)).permute(0, 2, 3, 1).reshape(-1, K)
+    _BF_CACHE[key] = r
+    return r
+
+
+def _bf_sums_arg(r, s):
+    return None if s == "nosums" else _bf_sums(r["dz"], r["xhat"], int(s[4:]))
+
+
+def _bf_conv_block(K=64):
+    """The producer of the pre-split legs, as in test_presplit_activation_chain: a 64 -> K streamed conv with the statistics
+    epilogue and the per-channel max / min image of its output y."""
+    if "conv" not in _BF_CACHE:
+        h = H()
+        xd = nhwc(rnd(2, 64, 16, 16, seed=601).clamp_(min=0))
+        wd = rnd(K, 64, 3, 3, seed=602, scale=(2.0 / (9 * 64)) ** 0.5).to(DEV)
+        wp, st = h.conv_weight(wd, "fwd", h.F16X3, xd, K)
+        assert st
+        y, stat = h.conv3x3_fwd(xd, wp, rnd(K, seed=603, scale=0.1).to(DEV), K, epi=h.EPI_BIAS_STATS, dtype=h.F16X3,
+                                streamed=True, want_bound=True)
+        _BF_CACHE["conv"] = (xd, wd, y, stat, y._egz_mm)
+    return _BF_CACHE["conv"]
+
+
+def _bf_fwg(h, B, Hh, Ww, C, K, s):
+    """egz_bn_bwd_first_wgrad: as test_first_block_backward_in_one_pass (test_hip_lf.py), 2e-5 against fp64 autograd."""
+    key = ("fwg", B, Hh, Ww, C, K)
+    x = rnd(B, C, Hh, Ww, seed=611)
+    if key not in _BF_CACHE:
+        w = rnd(K, C, 3, 3, seed=612, scale=0.3).double().requires_grad_(True)
+        y = F.conv2d(x.double(), w, None, padding=1)
+        gamma, beta = torch.rand(K, generator=torch.Generator().manual_seed(613)) + 0.5, rnd(K, seed=614, scale=0.2)
+        r = dict(_bf_block(key + ("bn",), y.detach().float(), gamma, beta, False, 615))
+        # the weight gradient of the conv under the block: dy of the block (for the fp32 y the kernels see) through the conv
+        y.backward(r["dy"])
+        r["dw"] = w.grad
+        _BF_CACHE[key] = r
+    r = _BF_CACHE[key]
+    dw, dg, db = h.bn_bwd_first_wgrad(r["yd"], r["dd"], r["coef"], x.to(DEV), sums=_bf_sums_arg(r, s))
+    errs = rel(dw.cpu(), r["dw"]), rel(dg.cpu(), r["dg"]), rel(db.cpu(), r["db"])
+    print("dw, dgamma, dbeta rel err", errs)
+    assert max(errs) < 2e-5
+
+
+def _bf_bwd(h, K, pool, s):
+    """egz_bn_relu_pool_bwd: the bars of test_bn_relu_pool (5e-5) against fp64 autograd."""
+    B, Hh, Ww = 2, 10, 16
+    y = rnd(B, K, Hh, Ww, seed=621) * 1.7 + 0.3
+    gamma, beta = torch.rand(K, generator=torch.Generator().manual_seed(622)) + 0.5, rnd(K, seed=623, scale=0.2)
+    r = _bf_block(("bwd", K, pool), y, gamma, beta, pool, 624)
+    dy, dg, db = h.bn_relu_pool_bwd(r["yd"], r["dd"], r["coef"], pool, sums=_bf_sums_arg(r, s))
+    errs = rel(nchw(dy), r["dy"]), rel(dg.cpu(), r["dg"]), rel(db.cpu(), r["db"])
+    print("dy, dgamma, dbeta rel err", errs)
+    assert max(errs) < 5e-5
+
+
+def _bf_bwd_pre(h, pool):
+    """egz_bn_relu_pool_bwd_presplit at K = 64, by the recipe of test_presplit_gradient_chain: dgamma / dbeta are those of the
+    fp32 launch, the bound holds and is tight, and the conv's data gradient takes the pairs (2e-6 against fp64)."""
+    xd, wd, y, stat, mm = _bf_conv_block()
+    B, Hh, Ww, K = y.shape
+    coef = h.bn_finalize(stat, float(B * Hh * Ww), (1.0 + 0.3 * rnd(K, seed=631)).to(DEV), (0.2 * rnd(K, seed=632)).to(DEV), None,
+                         None, 0.1, 1e-5)
+    dout = nhwc(rnd(B, K, Hh // 2 if pool else Hh, Ww // 2 if pool else Ww, seed=633, scale=3e-4))
+    assert h.presplit_grad_ok(B, Hh, Ww, 64, K)
+    dy_ref, dg_ref, db_ref = h.bn_relu_pool_bwd(y, dout, coef, pool)
+    dy_pre, dg_pre, db_pre = h.bn_relu_pool_bwd(y, dout, coef, pool, presplit=(h.absmax_of(dout), mm))
+    assert dy_pre._egz_presplit and torch.equal(dg_ref, dg_pre) and torch.equal(db_ref, db_pre)
+    true_max, bound = float(dy_ref.abs().max()), float(h.absmax_value(dy_pre._egz_absmax))
+    assert true_max <= bound <= 8 * true_max
+    wq, sq = h.conv_weight(wd, "dgrad", h.F16X3, dy_ref, 64)
+    dx_pre = h.conv3x3_dgrad(dy_pre, wq, 64, dtype=h.F16X3, streamed=sq, pre_in=True)
+    dxt = torch.nn.grad.conv2d_input((B, 64, Hh, Ww), wd.double().cpu(), nchw(dy_ref).double(), padding=1)
+    print("dx from pre-split dy, rel err", rel(nchw(dx_pre), dxt))
+    assert rel(nchw(dx_pre), dxt) < 2e-6
+    # ... and the fp32 launch it is measured against holds the bar of test_bn_relu_pool against fp64
+    y64, c64, d64 = nchw(y).double(), coef.double().cpu(), nchw(dout).double()
+    act = F.relu(y64 * c64[2].view(1, -1, 1, 1) + c64[3].view(1, -1, 1, 1)).requires_grad_(True)
+    (F.max_pool2d(act, 2, 2) if pool else act).backward(d64)
+    dz, xhat = act.grad * (act.detach() > 0), (y64 - c64[0].view(1, -1, 1, 1)) * c64[1].view(1, -1, 1, 1)
+    ref = c64[2].view(1, -1, 1, 1) * (dz - dz.mean((0, 2, 3), keepdim=True) - xhat * (dz * xhat).mean((0, 2, 3), keepdim=True))
+    assert rel(nchw(dy_ref), ref) < 5e-5
+
+
+def _bf_fwd(h, pool):
+    """egz_bn_relu_pool_fwd / _presplit at K = 64: the fp32 output against fp64 (1e-5, test_bn_relu_pool); the pairs give the
+    consumer conv the bits the fp32 tensor gives it (test_presplit_activation_chain)."""
+    xd, wd, y, stat, mm = _bf_conv_block()
+    B, Hh, Ww, K = y.shape
+    gam, bet = (1.0 + 0.3 * rnd(K, seed=641)).to(DEV), (0.2 * rnd(K, seed=642)).to(DEV)
+    coef, am = h.bn_finalize(stat, float(B * Hh * Ww), gam, bet, None, None, 0.1, 1e-5, mm=mm)
+    out_ref = h.bn_relu_pool_fwd(y, coef, pool)
+    ref = F.relu(F.batch_norm(nchw(y).double(), None, None, gam.double().cpu(), bet.double().cpu(), training=True, eps=1e-5))
+    assert rel(nchw(out_ref), F.max_pool2d(ref, 2, 2) if pool else ref) < 1e-5
+    assert float(h.absmax_value(am)) == float(h.absmax_value(out_ref._egz_absmax)) == float(out_ref.max())
+    out_pre = h.bn_relu_pool_fwd(y, coef, pool, presplit_am=am)
+    assert out_pre._egz_presplit and out_pre.shape == out_ref.shape
+    assert h.presplit_ok(B, out_ref.shape[1], out_ref.shape[2], K, 64)
+    w1, b1 = rnd(64, K, 3, 3, seed=643, scale=(2.0 / (9 * K)) ** 0.5).to(DEV), rnd(64, seed=644, scale=0.1).to(DEV)
+    wp1, st1 = h.conv_weight(w1, "fwd", h.F16X3, out_ref, 64)
+    assert st1
+    y_ref, s_ref = h.conv3x3_fwd(out_ref, wp1, b1, 64, epi=h.EPI_BIAS_STATS, dtype=h.F16X3, streamed=True)
+    y_pre, s_pre = h.conv3x3_fwd(out_pre, wp1, b1, 64, epi=h.EPI_BIAS_STATS, dtype=h.F16X3, streamed=True, pre_in=True)
+    assert torch.equal(y_ref, y_pre) and torch.equal(s_ref, s_pre)
+
+
+def _bf_fin(h, with_mm, rows):
+    """egz_bn_finalize / egz_bn_finalize_bound on `rows` partial rows (70: above RED_ROWS, folded first): the coefficient rows
+    against fp64 statistics (1e-5, the bar test_bn_relu_pool sets for what they produce); with the bound, the same bits and
+    the exact maximum of the block output (test_presplit_activation_chain)."""
+    xd, wd, y, stat, mm = _bf_conv_block()
+    B, Hh, Ww, K = y.shape
+    yc = y.reshape(-1, K).double().cpu()
+    parts = torch.stack([torch.stack([c.sum(0), (c * c).sum(0)]) for c in torch.tensor_split(yc, rows)]).to(DEV)
+    assert parts.shape == (rows, 2, K)
+    gam, bet = 1.0 + 0.3 * rnd(K, seed=651), 0.2 * rnd(K, seed=652)
+    rm, rv = rnd(K, seed=653, scale=0.1), torch.rand(K, generator=torch.Generator().manual_seed(654)) + 0.5
+    rmd, rvd, n = rm.clone().to(DEV), rv.clone().to(DEV), float(B * Hh * Ww)
+    got = h.bn_finalize(parts, n, gam.to(DEV), bet.to(DEV), rmd, rvd, 0.1, 1e-5, mm=mm if with_mm else None)
+    coef = got[0] if with_mm else got
+    mean, var = yc.mean(0), yc.var(0, unbiased=False)
+    invstd = 1.0 / torch.sqrt(var + 1e-5)
+    want = torch.stack([mean, invstd, gam.double() * invstd, bet.double() - mean * gam.double() * invstd])
+    errs = [rel(coef[i].cpu(), want[i]) for i in range(4)]
+    errs += [rel(rmd.cpu(), 0.9 * rm.double() + 0.1 * mean), rel(rvd.cpu(), 0.9 * rv.double() + 0.1 * yc.var(0, unbiased=True))]
+    print("mean, invstd, scale, shift, running mean, running var rel err", errs)
+    assert max(errs) < 1e-5
+    if with_mm:
+        plain = h.bn_finalize(parts, n, gam.to(DEV), bet.to(DEV), None, None, 0.1, 1e-5)
+        assert torch.equal(coef, plain)
+        assert float(h.absmax_value(got[1])) == float(h.bn_relu_pool_fwd(y, coef, False).max())
+
+
+def _bf_first(h, B, Hh, Ww, C, K, stats):
+    """egz_conv_first_fwd: the direct kernel (C <= 3) at the bars of test_conv_first_direct_32_filters, the MFMA kernel at those
+    of test_conv_first; with and without the statistics epilogue."""
+    x, w, b = rnd(B, C, Hh, Ww, seed=661), rnd(K, C, 3, 3, seed=662, scale=(2.0 / (9 * C)) ** 0.5), rnd(K, seed=663, scale=0.1)
+    ref = F.conv2d(x.double(), w.double(), b.double(), padding=1)
+    tol_y, tol_s = (2e-6, 1e-6) if C <= 3 else (2e-5, 1e-5)
+    y, stat = h.conv_first_fwd(x.to(DEV), w.to(DEV), b.to(DEV), stats)
+    assert rel(nchw(y), ref) < tol_y
+    if stats:
+        assert stat.shape[0] == h.LIB.egz_conv_first_stat_rows_for(B, Hh, Ww, C, K)
+        s = stat.sum(0).cpu()
+        assert rel(s[0], ref.sum(dim=(0, 2, 3))) < tol_s and rel(s[1], (ref ** 2).sum(dim=(0, 2, 3))) < tol_s
+    else:
+        assert stat is None
+
+
+def _bf_first_wgrad(h, B, Hh, Ww, C, K):
+    """egz_conv_first_wgrad: 2e-5 against the fp64 weight gradient (test_conv_first)."""
+    x, dy = rnd(B, C, Hh, Ww, seed=671), rnd(B, K, Hh, Ww, seed=672)
+    w = torch.zeros(K, C, 3, 3, dtype=torch.float64, requires_grad=True)
+    F.conv2d(x.double(), w, None, padding=1).backward(dy.double())
+    assert rel(h.conv_first_wgrad(x.to(DEV), nhwc(dy)).cpu(), w.grad) < 2e-5
+
+
+_BF_RUN = {"fwg": _bf_fwg, "bwd": _bf_bwd, "bwd_pre": _bf_bwd_pre, "fwd": _bf_fwd, "fin": _bf_fin, "first": _bf_first,
+           "first_wgrad": _bf_first_wgrad}
+
+
+@pytest.mark.parametrize("leg", BN_FIRST_LEGS, ids=[l[0] for l in BN_FIRST_LEGS])
+def test_bn_first_dispatch_legs(leg, monkeypatch):
+    """Every instantiation the host code of csrc/bn_pool.hip and csrc/conv_first.hip can pick, once, at the smallest shape that
+    picks it, against fp64 torch at the bars this file and test_hip_lf.py already hold these ops to:
+    bn_bwd_first_wgrad over Cin x pixels per thread (by W) x filter quads x {own reduce pass (also one that writes more than
+    RED_ROWS rows); 3 partial rows: in-kernel finalize; 520 rows: fold + finalize launch}; bn_relu_pool_bwd over pool x K (fused
+    apply or not, one or two rows per block) x the same three sources of the sums, and its pre-split form; bn_relu_pool_fwd and
+    its pre-split form; bn_finalize with and without the bound, with and without the fold; conv_first_fwd over Cin x pixels per
+    thread x filters x statistics, on the direct and on the MFMA kernel; conv_first_wgrad over both reduction widths x filters."""
+    h = H()
+    monkeypatch.setattr(h, "SPLITK", False)              # (the producer conv of the pre-split legs: as the chain tests)
+    _BF_RUN[leg[1]](h, *leg[2])
