@@ -214,7 +214,10 @@ class _GraphedSampleStep:
 class AT():
     def __init__(self, pretrained_model=None, pretrained_lstm=None, extract_lstm=False, crop_size=3,
                  num_epoch_lstm=30, lstm_save_img='loss_lstm.png', save_path='save', save_name='best_lstm.pth.tar',
-                 device='0', lstm_data_path='../512w', traindata=None, valdata=None, task=None, align=False):
+                 device='0', lstm_data_path='../512w', traindata=None, valdata=None, task=None, align=False,
+                 shard=None):
+        """``shard=(rank, world)``: with ``extract_lstm`` every rank of the default process group extracts its share of the
+        LSTM training data (extractLSTMw.extractw), then all meet at a barrier so that each lists the complete folders."""
         if pretrained_model is None:
             raise generalException('AT module have to use pretrained SP module.')
         self.device = torch.device('cuda:' + device)
@@ -226,7 +229,10 @@ class AT():
         if extract_lstm:
             from .extractLSTMw import extract_LSTM_training_data
             extract_LSTM_training_data(save_path=lstm_data_path, trained_model=pretrained_model, device=device,
-                                       crop_size=crop_size, traindata=traindata, valdata=valdata, align=align)
+                                       crop_size=crop_size, traindata=traindata, valdata=valdata, align=align, shard=shard)
+            if shard is not None:
+                from . import dp
+                dp.barrier()
         self.crop_size, self.num_epoch_lstm, self.epochnow = crop_size, num_epoch_lstm, 0
         self.lstm_save_img, self.save_path, self.save_name = lstm_save_img, save_path, save_name
         self.lstm_data_path, self.batch_size, self.align = lstm_data_path, 1, align
@@ -365,7 +371,7 @@ class AT():
             plot_loss(loss_train, loss_val, os.path.join(self.save_path, self.lstm_save_img))
         print('lstm training finished!')
 
-    def extract_late(self, st_loader, pred_folder='../new_pred/', feat_folder='../new_feat/', chunk=32):
+    def extract_late(self, st_loader, pred_folder='../new_pred/', feat_folder='../new_feat/', chunk=32, shard=None):
         """pred = SP gaze map, feat = AT-weighted conv5_3 map, both written as uint8 PNGs (AT.py:199-253).
 
         The same sequential LSTM state as the reference's batch-1 loop, but the frames of the (batch-1) loader are gathered
@@ -377,7 +383,23 @@ class AT():
         and ``(255 * output).to(uint8)`` truncates: a 1-ulp difference next to an integer flips that pixel by one level.
         Against the reference's own output the chunked path differs by +-1 LSB on < 0.2 % of the pixels
         (tests/test_hip_config5.py), the same class of difference as chunk=1 vs the reference's CPU arithmetic; pass
-        ``chunk=1`` when the written PNGs must not depend on the batching."""
+        ``chunk=1`` when the written PNGs must not depend on the batching.
+
+        ``shard=(rank, world)``: this process is one of ``world`` ranks of the default process group and extracts its share.
+        The chunks are dealt out by chunk index (dp.chunk_shards: chunk k on rank k % world), so every frame sits in the chunk
+        it has in a one-rank run with the same ``chunk`` -- same launches, same bits.  Per window of ``world`` chunks a rank
+        stages and forwards its own chunk only (stage A), the crop means and fixation flags of all chunks are all-gathered,
+        EVERY rank runs the window's LSTM calls in chunk order (so the carried state is the same everywhere, bit for bit)
+        and keeps the outputs of its own chunk, then weights, quantises and writes its own frames (stage B).  Each rank
+        loads only its own frames, through a loader built over its indices of ``st_loader.dataset`` (a shuffling loader is
+        refused).  The files written are byte for byte those of ``shard=None``; ``shard=(0, 1)`` needs no process group."""
+        from . import dp
+        cap = max(1, int(chunk))
+        plan = None
+        if shard is not None:
+            rank_, world_ = dp.check_shard(shard)
+            plan = dp.chunk_shards(len(getattr(st_loader, 'dataset', ())), cap, world_)
+            st_loader = dp.owned_loader(st_loader, plan.indices(rank_))
         print('begin to extract files for training LF module ...')
         os.makedirs(pred_folder, exist_ok=True)
         os.makedirs(feat_folder, exist_ok=True)
@@ -430,10 +452,8 @@ class AT():
 
         dev_ = self.device
 
-        def launch(ch):
-            """Queue the whole device side of a chunk; nothing here waits for the GPU."""
-            nonlocal hidden
-            n = len(ch.samples)
+        def stage_a(ch, n):
+            """Own frames up to the crop means: normalise, SP forward, uint8 quantisation, gaze point, crop means (n,512)."""
             t0 = time.perf_counter()
             if copy_stream is not None:
                 torch.cuda.current_stream().wait_stream(copy_stream)
@@ -457,17 +477,27 @@ class AT():
                 chn_weights = crop_align_mean(feature_s, pred_gp, self.crop_size)            # (n,512)
             else:
                 chn_weights = crop_mean_weight(feature_s, pred_gp, self.crop_size)           # (n,512)
-            t0 = mark("crop", t0)
-            # The recurrent part.  A fixation frame (fixsac == 1) keeps its crop mean and leaves the state alone; the saccade
-            # frames of the chunk, in order, are ONE lstmnet call over T' = their count steps at batch 1 (inputs known up front,
-            # state carried in and out): the same recurrence as the reference's frame-by-frame calls (AT.py:240-246).
-            sacc = [i for i, sm in enumerate(ch.samples) if int(sm['fixsac']) != 1]
-            if sacc:
-                idx = torch.tensor(sacc, device=chn_weights.device)
-                hidden = repackage_hidden(hidden)
-                seq, hidden = self.lstm(chn_weights.index_select(0, idx).unsqueeze(1), hidden)      # (T',1,512)
-                chn_weights = chn_weights.index_copy(0, idx, seq.squeeze(1))
-            t0 = mark("lstm", t0)
+            mark("crop", t0)
+            return quant, feature_s, chn_weights
+
+        def chain(rows, flags):
+            """The recurrent part of ONE chunk.  A fixation frame (fixsac == 1) keeps its crop mean and leaves the state alone;
+            the saccade frames of the chunk, in order, are ONE lstmnet call over T' = their count steps at batch 1 (inputs
+            known up front, state carried in and out): the same recurrence as the reference's frame-by-frame calls
+            (AT.py:240-246).  ``rows`` (n,512) crop means, ``flags`` the frames' int(fixsac) -> (saccade indices, (T',512))
+            or (None, None) when the chunk has no saccade frame (no call, the state stays)."""
+            nonlocal hidden
+            sacc = [i for i, f in enumerate(flags) if f != 1]
+            if not sacc:
+                return None, None
+            idx = torch.tensor(sacc, device=rows.device)
+            hidden = repackage_hidden(hidden)
+            seq, hidden = self.lstm(rows.index_select(0, idx).unsqueeze(1), hidden)      # (T',1,512)
+            return idx, seq.squeeze(1)
+
+        def stage_b(ch, n, quant, feature_s, chn_weights):
+            """Own frames from the final channel weights on: weighted maps, quantisation, asynchronous read-back."""
+            t0 = time.perf_counter()
             feats = get_weighted_batch(chn_weights, feature_s)        # (n,14,14): one launch for the chunk (AT.py:58-66 per frame)
             featq = (255 * feats).to(torch.uint8)                     # np.uint8(255 * x) on the device
             if self.device.type == 'cuda':
@@ -481,6 +511,46 @@ class AT():
             else:
                 ch.out, ch.done = (quant, featq), None
             mark("weighted_readback", t0)
+
+        def launch(ch):
+            """Queue the whole device side of a chunk; nothing here waits for the GPU."""
+            n = len(ch.samples)
+            quant, feature_s, chn_weights = stage_a(ch, n)
+            t0 = time.perf_counter()
+            idx, seq = chain(chn_weights, [int(sm['fixsac']) for sm in ch.samples])
+            if idx is not None:
+                chn_weights = chn_weights.index_copy(0, idx, seq)
+            mark("lstm", t0)
+            stage_b(ch, n, quant, feature_s, chn_weights)
+
+        def launch_window(ch, w):
+            """The sharded form of launch(): ``ch`` is this rank's chunk of the window (possibly empty).  The one point that
+            waits is the gather: the fixation flags are host data every rank needs before it can shape the LSTM calls, and a
+            backend without device collectives is fed the crop means from host memory."""
+            n = len(ch.samples)
+            if n:
+                quant, feature_s, chn_weights = stage_a(ch, n)
+            t0 = time.perf_counter()
+            rows = torch.zeros((cap, 512), dtype=torch.float32, device=self.device)      # rows padded to the chunk size
+            meta = torch.zeros(cap + 1, dtype=torch.int32)                                # row count, then int(fixsac) per row
+            if n:
+                rows[:n].copy_(chn_weights)
+                meta[0] = n
+                meta[1:n + 1] = torch.tensor([int(sm['fixsac']) for sm in ch.samples], dtype=torch.int32)
+            all_meta = [m.tolist() for m in dp.all_gather(meta)]
+            all_rows = dp.all_gather(rows)
+            t0 = mark("gather", t0)
+            for r in range(world_):
+                n_r = all_meta[r][0]
+                if n_r != len(plan.window(w, r)):
+                    raise RuntimeError(f"sharded extract_late: rank {r} brought {n_r} frames to window {w}, "
+                                       f"the plan gives it {len(plan.window(w, r))}")
+                idx, seq = chain(all_rows[r][:n_r], all_meta[r][1:n_r + 1])
+                if r == rank_ and idx is not None:
+                    chn_weights = chn_weights.index_copy(0, idx, seq)
+            mark("lstm", t0)
+            if n:
+                stage_b(ch, n, quant, feature_s, chn_weights)
 
         def finish(ch):
             """Hand the images of a queued chunk over (host I/O) once its results have landed."""
@@ -499,25 +569,34 @@ class AT():
             if prof is not None:
                 prof["finish_host"] = prof.get("finish_host", 0.0) + time.perf_counter() - t0
 
-        cap = max(1, int(chunk))
         ring, cur, prev = [_Chunk(), _Chunk()], 0, None
         kept = getattr(self, "_extract_buffers", None)               # device / pinned buffers survive across calls
         if kept is not None:
             for ch, (bufs, sig, out) in zip(ring, kept):
                 ch.bufs, ch.sig, ch.out = bufs, sig, out
+
+        def step(queue, *at):
+            """Queue the staged chunk, then hand over the one queued before it."""
+            nonlocal cur, prev
+            queue(ring[cur], *at)
+            if prev is not None:
+                finish(ring[prev])
+            prev, cur = cur, 1 - cur
+
         with torch.no_grad():
-            for i, sample in _progress(enumerate(st_loader)):
-                ring[cur].add(to_raw_u8(sample, self.device), cap)
-                if len(ring[cur].samples) >= cap:
-                    launch(ring[cur])
-                    if prev is not None:
-                        finish(ring[prev])
-                    prev, cur = cur, 1 - cur
-            if ring[cur].samples:
-                launch(ring[cur])
-                if prev is not None:
-                    finish(ring[prev])
-                prev = cur
+            if plan is None:
+                for i, sample in _progress(enumerate(st_loader)):
+                    ring[cur].add(to_raw_u8(sample, self.device), cap)
+                    if len(ring[cur].samples) >= cap:
+                        step(launch)
+                if ring[cur].samples:
+                    step(launch)
+            else:
+                frames = iter(st_loader)
+                for w in _progress(range(plan.windows)):
+                    for _ in plan.window(w, rank_):
+                        ring[cur].add(to_raw_u8(next(frames), self.device), cap)
+                    step(launch_window, w)
             if prev is not None:
                 finish(ring[prev])
         self._extract_buffers = [(ch.bufs, ch.sig, ch.out) for ch in ring]

@@ -251,6 +251,102 @@ def barrier():
         dist.barrier()
 
 
+class ChunkShards:
+    """How ``n`` frames, cut into consecutive chunks of ``chunk`` frames (the last one possibly shorter), are dealt out to
+    ``world`` ranks: chunk k belongs to rank k % world, window w is chunks w * world ... w * world + world - 1, and every
+    rank walks the same number of windows (a collective per window needs that) -- in the last one a rank may own a short
+    chunk or none.  Dealt by CHUNK INDEX, not by a frame range per rank: a batched SP forward is not bitwise equal across
+    batch compositions (AT.extract_late), so every frame must sit in exactly the chunk it has in a one-rank run."""
+
+    def __init__(self, n: int, chunk: int, world: int):
+        n, chunk, world = int(n), int(chunk), int(world)
+        if n < 0:
+            raise ValueError(f"chunk_shards: n must be >= 0, got {n}")
+        if chunk < 1:
+            raise ValueError(f"chunk_shards: chunk must be >= 1, got {chunk}")
+        if world < 1:
+            raise ValueError(f"chunk_shards: world must be >= 1, got {world}")
+        self.n, self.chunk, self.world = n, chunk, world
+        self.n_chunks = (n + chunk - 1) // chunk
+        self.windows = (self.n_chunks + world - 1) // world
+
+    def _rank(self, rank_: int) -> int:
+        if not 0 <= int(rank_) < self.world:
+            raise ValueError(f"chunk_shards: rank {rank_} is outside a world of {self.world}")
+        return int(rank_)
+
+    def frames(self, k: int) -> range:
+        """Frame indices of chunk ``k`` (empty past the last chunk)."""
+        if k < 0:
+            raise ValueError(f"chunk_shards: chunk index must be >= 0, got {k}")
+        return range(min(self.n, k * self.chunk), min(self.n, (k + 1) * self.chunk))
+
+    def owner(self, k: int) -> int:
+        return k % self.world
+
+    def window(self, w: int, rank_: int) -> range:
+        """Frame indices of the chunk ``rank_`` owns in window ``w`` (empty: no chunk there)."""
+        if not 0 <= w < max(self.windows, 1):
+            raise ValueError(f"chunk_shards: window {w} is outside {self.windows} windows")
+        return self.frames(w * self.world + self._rank(rank_))
+
+    def indices(self, rank_: int) -> List[int]:
+        """All frame indices of ``rank_``, in the order it meets them (increasing)."""
+        r = self._rank(rank_)
+        return [i for w in range(self.windows) for i in self.frames(w * self.world + r)]
+
+
+def chunk_shards(n: int, chunk: int, world: int) -> ChunkShards:
+    return ChunkShards(n, chunk, world)
+
+
+def check_shard(shard):
+    """``shard=(rank, world)`` of an extraction pass -> (rank, world) as ints; it has to name this process's place in the
+    default process group (world 1 needs none)."""
+    rank_, world_ = (int(v) for v in shard)
+    if world_ < 1 or not 0 <= rank_ < world_:
+        raise ValueError(f"shard=(rank, world) = {tuple(shard)}: need world >= 1 and 0 <= rank < world")
+    if world_ > 1 and (world_size(), rank()) != (world_, rank_):
+        raise ValueError(f"shard={tuple(shard)} is not this process's place in the default process group "
+                         f"(rank {rank()} of {world_size()})")
+    return rank_, world_
+
+
+def all_gather(t: torch.Tensor) -> List[torch.Tensor]:
+    """``t`` of every rank (same shape and dtype everywhere) as a list indexed by rank, on ``t``'s device.  RCCL gathers
+    device tensors in stream order; any other backend is fed from host memory (as sync_buffers does), which waits for the
+    work that produces ``t``.  The bits are not touched either way.  Without a process group: ``[t]``."""
+    world = world_size()
+    if world == 1:
+        return [t]
+    if t.is_cuda == (dist.get_backend() == "nccl"):
+        out = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(out, t.contiguous())
+        return out
+    side = t.detach().cpu() if t.is_cuda else t.detach().cuda()
+    out = [torch.empty_like(side) for _ in range(world)]
+    dist.all_gather(out, side.contiguous())
+    return [o.to(t.device) for o in out]
+
+
+def owned_loader(loader, indices):
+    """A loader over ``indices`` of ``loader.dataset``, in that order, with ``loader``'s batch size 1, collate_fn, pin_memory
+    and worker count: a rank of a sharded extraction decodes and uploads only its own frames.  Refuses a loader whose order
+    is not the dataset's: the plan deals frames out by dataset index."""
+    from torch.utils.data import DataLoader, SequentialSampler, Subset
+    if not isinstance(loader, DataLoader):
+        raise TypeError("a sharded extraction builds a loader over this rank's own indices of st_loader.dataset: "
+                        f"it needs a torch DataLoader, not {type(loader).__name__}")
+    if not isinstance(loader.sampler, SequentialSampler):
+        raise ValueError("a sharded extraction refuses a loader that shuffles (sampler "
+                         f"{type(loader.sampler).__name__}): frames are dealt to the ranks by dataset index so that every "
+                         "frame sits in the chunk it has in a one-rank run, and the LSTM state is carried in that order")
+    if loader.batch_size != 1:
+        raise ValueError(f"a sharded extraction stages frame by frame: the loader's batch size must be 1, got {loader.batch_size}")
+    return DataLoader(Subset(loader.dataset, list(indices)), batch_size=1, shuffle=False, num_workers=loader.num_workers,
+                      pin_memory=loader.pin_memory, collate_fn=loader.collate_fn)
+
+
 class RankShardSampler(torch.utils.data.Sampler):
     """Shards a dataset over the ranks: rank r takes indices r, r+world, ... of a (per-epoch seeded) permutation.
 

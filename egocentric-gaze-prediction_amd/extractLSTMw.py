@@ -81,36 +81,74 @@ def channel_weight(feat, gt, crop_size, align):
     return crop.view(crop.size(0), crop.size(1), -1).mean(2).squeeze(0)
 
 
-def extractw(loader, model, savepath, crop_size=3, device='0', align=False):
+class _SecondFrame:
+    """The fixation state machine (extractLSTMw.py:74-111) fed one flag per frame: the first frame of a fixation arms it,
+    the second is the one to extract (True), the rest are skipped until a saccade frame."""
+    OUT, ARMED, TAKEN = 0, 1, 2           # no fixation / first fixation frame seen / second frame extracted
+
+    def __init__(self):
+        self.state = self.OUT
+
+    def __call__(self, flag):
+        fix = float(flag) == 1.0
+        if self.state == self.OUT:
+            self.state = self.ARMED if fix else self.OUT
+        elif self.state == self.ARMED:
+            if not fix:
+                raise RuntimeError('fixation is not processed.')       # extractLSTMw.py:110-111
+            self.state = self.TAKEN
+            return True
+        elif not fix:
+            self.state = self.OUT
+        return False
+
+
+def fixation_second_frames(flags):
+    """Indices of the frames extractw extracts, from the fixation flags alone."""
+    second = _SecondFrame()
+    return [i for i, f in enumerate(flags) if second(f)]
+
+
+def _shard_loader(loader, shard):
+    """The loader of one rank of a sharded extractw: over every ``world``-th of the frames a one-rank run extracts.  Which
+    frames those are depends on the flags of ALL frames, so they are read from ``dataset.fixsac`` (STDataset keeps them in
+    memory) -- loading every frame on every rank just for its flag would undo the sharding."""
+    from . import dp
+    rank_, world_ = dp.check_shard(shard)
+    flags = getattr(getattr(loader, 'dataset', None), 'fixsac', None)
+    if flags is None or len(flags) != len(loader.dataset):
+        raise ValueError("a sharded extractw picks the second frame of every fixation before it loads a frame: the dataset "
+                         "has to keep one fixation flag per sample in ``dataset.fixsac`` (as STDataset does)")
+    return dp.owned_loader(loader, fixation_second_frames(flags)[rank_::world_])
+
+
+def extractw(loader, model, savepath, crop_size=3, device='0', align=False, shard=None):
+    """``shard=(rank, world)``: this rank extracts every ``world``-th of the frames a one-rank run extracts and loads no
+    others (frames are independent and forwarded at batch 1, so its files are the one-rank run's bit for bit); no
+    collective, and file names are per frame, so ranks never collide."""
     dev = torch.device(device if str(device).startswith(('cuda', 'cpu')) else 'cuda:' + str(device))
+    second = _SecondFrame()
+    if shard is not None:
+        loader, second = _shard_loader(loader, shard), (lambda flag: True)
     print('extracting lstm training data...')
     os.makedirs(savepath, exist_ok=True)
-    OUT, ARMED, TAKEN = 0, 1, 2           # no fixation / first fixation frame seen / second frame extracted
-    state = OUT
     with torch.no_grad():
         for i, sample in enumerate(loader):
-            fix = float(sample['fixsac']) == 1.0
-            if state == OUT:
-                state = ARMED if fix else OUT
-            elif state == ARMED:
-                if not fix:
-                    raise RuntimeError('fixation is not processed.')       # extractLSTMw.py:110-111
-                state = TAKEN
-                if 'jpeg_blob' in sample:          # decode='gpu': the host path's normalised fields, decoded on the device
-                    from .data.STdatas import check_decode_status, stage_batch
-                    image, _, gt = stage_batch(sample, dev)
-                    check_decode_status(sample)
-                    sample = dict(sample, image=image, gt=gt.cpu())
-                feat = model(sample['image'].float().to(dev))                      # (1,512,14,14)
-                w = channel_weight(feat, sample['gt'], crop_size, align).cpu()
-                torch.save(w, os.path.join(savepath, 'fix_' + sample['imname'][0][:-4] + '.pth.tar'))
-            elif not fix:
-                state = OUT
+            if not second(sample['fixsac']):
+                continue
+            if 'jpeg_blob' in sample:          # decode='gpu': the host path's normalised fields, decoded on the device
+                from .data.STdatas import check_decode_status, stage_batch
+                image, _, gt = stage_batch(sample, dev)
+                check_decode_status(sample)
+                sample = dict(sample, image=image, gt=gt.cpu())
+            feat = model(sample['image'].float().to(dev))                      # (1,512,14,14)
+            w = channel_weight(feat, sample['gt'], crop_size, align).cpu()
+            torch.save(w, os.path.join(savepath, 'fix_' + sample['imname'][0][:-4] + '.pth.tar'))
     print('done')
 
 
 def extract_LSTM_training_data(save_path='../512w', trained_model='save/best_fusion.pth.tar', device='0', crop_size=3,
-                               traindata=None, valdata=None, align=False):
+                               traindata=None, valdata=None, align=False, shard=None):
     model = make_layers(cfg['D'], 3)
     sd = torch.load(trained_model, map_location='cpu', weights_only=False)['state_dict']
     own = model.state_dict()
@@ -120,5 +158,5 @@ def extract_LSTM_training_data(save_path='../512w', trained_model='save/best_fus
     for data, sub in ((traindata, 'train'), (valdata, 'test')):
         loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
                             collate_fn=getattr(data, 'collate_fn', None))
-        extractw(loader, model, os.path.join(save_path, sub), crop_size, device, align)
+        extractw(loader, model, os.path.join(save_path, sub), crop_size, device, align, shard=shard)
     print('Attention weight for training LSTMnet successfully extracted.')

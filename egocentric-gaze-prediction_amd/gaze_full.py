@@ -78,6 +78,37 @@ def _at_stage(args, STTrainData, STValData):
                              args.extract_late_pred_folder, args.extract_late_feat_folder)
 
 
+def _at_stage_sharded(args, STTrainData, STValData):
+    """The AT stage under torch.distributed.  The two extraction passes are per-frame work and run on every rank
+    (extractLSTMw.extractw and AT.extract_late with ``shard=``); ``AT.train`` is a per-sample optimiser chain whose state and
+    weights are carried from sample to sample across the whole dataset, so it stays on rank 0 while the others wait on
+    the host (_wait_for_rank0)."""
+    from . import dp
+    from .AT import AT
+    shard = (dp.rank(), dp.world_size())
+    att = AT(pretrained_model=args.pretrained_model, pretrained_lstm=args.pretrained_lstm,
+             extract_lstm=args.extract_lstm, crop_size=args.crop_size, num_epoch_lstm=args.num_epoch_lstm,
+             lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
+             device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
+             task=args.task, align=args.align, shard=shard)
+    if args.train_lstm:
+        if dp.is_main():
+            try:
+                att.train()
+            except BaseException:         # let the waiting ranks go down with this one instead of polling for ever
+                torch.distributed.distributed_c10d._get_default_store().set("at_lstm_trained/failed", "1")
+                raise
+        _wait_for_rank0("at_lstm_trained")
+    if args.extract_late:
+        # every rank runs the whole recurrence of extract_late: all of them take the weights from the one saved file
+        att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
+        for data in (STValData, STTrainData):
+            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
+                                        collate_fn=getattr(data, 'collate_fn', None)),
+                             args.extract_late_pred_folder, args.extract_late_feat_folder, shard=shard)
+    dp.barrier()                          # LF lists the folders: not before every rank has written its files
+
+
 def _wait_for_rank0(key, poll_s=5.0):
     """Host-side rendezvous after a rank-0-only stage: rank 0 sets ``key`` in the default process group's store when it is
     done (or ``key + '/failed'`` on its way out of an exception), the others poll with sleep.  No device collective runs
@@ -109,7 +140,7 @@ def main(argv=None):
         import datetime
         args.device = os.environ['LOCAL_RANK']
         torch.cuda.set_device(int(args.device))
-        # the AT stage below is sequential (rank 0 only) and takes hours: the other ranks wait for it on the HOST
+        # the LSTM training of the AT stage is sequential (rank 0 only) and takes hours: the other ranks wait for it on the HOST
         # (_wait_for_rank0: a key in the process group's store, polled with sleep) -- not inside a device collective, which
         # would spin for hours and need a multi-day collective timeout that also hides real hangs of the SP / LF all-reduces
         torch.distributed.init_process_group(os.environ.get('EGAZE_DIST_BACKEND', 'nccl'),
@@ -133,17 +164,13 @@ def main(argv=None):
                 pretrained_temporal=args.pretrained_temporal, traindata=STTrainData, valdata=STValData)
         sp.train()
         args.pretrained_model = os.path.join(args.save_path, args.save_sp)
-    # AT is a batch-1, sequence-1 recurrence whose hidden state is carried from sample to sample across the whole
-    # dataset (AT.py:127-145, 199-253): it does not shard without changing its results, so under torch.distributed it
-    # runs on rank 0 only (which also owns every file it writes) while the other ranks wait.
-    if dp.is_main():
-        try:
-            _at_stage(args, STTrainData, STValData)
-        except BaseException:
-            if dp.world_size() > 1:       # let the waiting ranks go down with this one instead of polling for ever
-                torch.distributed.distributed_c10d._get_default_store().set("at_stage_done/failed", "1")
-            raise
-    _wait_for_rank0("at_stage_done")
+    # Under torch.distributed the AT stage's two extraction passes are sharded over the ranks, chunk by chunk, without changing
+    # a byte of what they write; only the LSTM training -- a batch-1, sequence-1 optimiser chain carried from sample to sample
+    # across the whole dataset (AT.py:127-145) -- runs on rank 0 alone (_at_stage_sharded).  One rank: the calls as ever.
+    if dp.world_size() == 1:
+        _at_stage(args, STTrainData, STValData)
+    else:
+        _at_stage_sharded(args, STTrainData, STValData)
     lf = LF(pretrained_model=args.pretrained_late, save_path=args.save_path, late_save_img=args.late_save_img,
             save_name=args.save_late, device=args.device, late_pred_path=args.extract_late_pred_folder,
             num_epoch=args.num_epoch, late_feat_path=args.extract_late_feat_folder, gt_path=args.gtPath,
