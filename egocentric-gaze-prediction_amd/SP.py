@@ -58,10 +58,11 @@ class SP():
         self.train_sampler = dp.RankShardSampler(traindata, True, batch_size) if dp.world_size() > 1 else None
         val_sampler = dp.RankShardSampler(valdata, False, batch_size, pad=False) if dp.world_size() > 1 else None
         self.STTrainLoader = DataLoader(dataset=traindata, batch_size=batch_size, shuffle=self.train_sampler is None,
-                                        sampler=self.train_sampler, num_workers=1, pin_memory=True,
+                                        sampler=self.train_sampler, num_workers=getattr(traindata, 'loader_workers', 1),
+                                        pin_memory=True,
                                         collate_fn=getattr(traindata, 'collate_fn', None))
         self.STValLoader = DataLoader(dataset=valdata, batch_size=batch_size, shuffle=False, sampler=val_sampler,
-                                      num_workers=1, pin_memory=True,
+                                      num_workers=getattr(valdata, 'loader_workers', 1), pin_memory=True,
                                       collate_fn=getattr(valdata, 'collate_fn', None))
         in_channels = 20
         self.model = model_SP(make_layers(cfg['D'], 3), make_layers(cfg['D'], in_channels))

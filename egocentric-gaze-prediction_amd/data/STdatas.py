@@ -34,6 +34,8 @@ def stage_batch(sample, device):
     """('image', 'flow', 'gt') of a collated sample as normalised fp32 tensors on ``device``.  A dataset built with
     ``raw_u8=True`` hands over bytes: they cross PCIe at a quarter of the fp32 size and are normalised by
     ``egz_u8_normalize`` with the reference's own three fp32 operations (bit-exact with the host expression below)."""
+    if 'resident' in sample:            # data.resident: the planes are on the device already, one gather launch builds the batch
+        return sample['resident'].gather(sample, device, fields=('image', 'flow', 'gt'))
     if 'jpeg_blob' in sample:           # decode='gpu': one H2D copy, one decode launch, then the raw_u8 path below
         from .. import hipops as H
         image, flow, gt = decode_to_u8(sample, device)
@@ -231,7 +233,13 @@ def decode_to_u8(sample, device):
 def check_decode_status(sample):
     """Reads the status words of a decode_to_u8 batch (waits for that batch's decode only): corrupt data warns, as cv2 does, and
     keeps the partially decoded image; an unsupported file or a size mismatch raises.  No-op for other samples."""
-    pending = sample.pop('_jpeg_status', None) if isinstance(sample, dict) else None
+    if not isinstance(sample, dict):
+        return
+    resident = sample.pop('_resident_status', None)
+    if resident is not None:               # data.resident: the gather skipped a sample whose index was out of range
+        from ..hipops import check_resident_status
+        check_resident_status(resident)
+    pending = sample.pop('_jpeg_status', None)
     if pending is None:
         return
     host, ev = pending
@@ -249,6 +257,13 @@ def check_decode_status(sample):
 def to_raw_u8(sample, device):
     """A decode='gpu' batch in the layout of a ``raw_u8`` batch on ``device`` (uint8 'image' / 'flow' / 'gt', the other
     fields as they are), status words checked; other batches are returned unchanged.  For consumers that index the fields."""
+    if 'resident' in sample:               # data.resident: the bytes gathered from the pool, no file is read
+        raw = sample['resident'].gather(sample, device, raw=True)
+        check_decode_status(sample)
+        image, flow, gt = raw[:, :3], raw[:, 3:23], raw[:, 23:]
+        if raw.shape[0] > 1:
+            image, flow, gt = image.contiguous(), flow.contiguous(), gt.contiguous()
+        return {'image': image, 'flow': flow, 'gt': gt, 'fixsac': sample['fixsac'], 'imname': sample['imname']}
     if 'jpeg_blob' not in sample:
         return sample
     image, flow, gt = decode_to_u8(sample, device)

@@ -1,0 +1,204 @@
+"""The decoded dataset resident in HBM (``--gpu_resident``): every distinct file of an ``STDataset`` is decoded ONCE into a
+uint8 plane pool on the device, and a batch is one gather launch over that pool (hipops.resident_gather: gather, the three
+normalisations, the flow stack's NHWC-32 form and its abs-max).  Per frame the distinct data is one colour image, one flow_x,
+one flow_y and one ground-truth map -- 6 planes -- while a sample reads 24 planes from 22 files and consecutive samples share 18
+of their 20 flow files; the loop then does no decode, no PCIe copy of pixels and no re-read of the flow window.  DESIGN.md
+section 15 has the memory arithmetic.
+
+A sample of this dataset is its number; the collated batch carries the numbers and the dataset, and the two staging choke
+points (data.STdatas.stage_batch / to_raw_u8, streamtrain.stage_stream) turn it into tensors.  The DataLoader, its samplers and
+their RNG draws are those of the host dataset, so a seeded run visits the same samples in the same batches."""
+import time
+import warnings
+
+import numpy as np
+import torch
+
+from ._io import imread
+from .STdatas import STDataset, sniff
+
+COLS = 22                                   # table columns: image, 20 flow planes, ground truth
+
+
+class ResidentSTDataset(STDataset):
+    """``STDataset`` whose planes live on the device.  ``decode`` selects how ``fill`` decodes ('gpu': hipops.jpeg_decode
+    for the files ``sniff`` takes, the host for the rest); ``gpu_fields`` is honoured as in ``STDataset``: files of a field
+    not in it are neither read nor given planes.  Usage: ``ds.fill(device)`` once, then any DataLoader with
+    ``collate_fn=ds.collate_fn`` and ``num_workers=ds.loader_workers``."""
+    loader_workers = 0                      # the pool must not be pickled into a worker
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.collate_fn = self._collate
+        self.pool = self.table = None       # device tensors after fill()
+        self._plan = None
+
+    # ------------------------------------------------------------------ plan (host only)
+    def plan(self):
+        """Lists the distinct files of the fields in use, gives each its planes in the pool and builds the (N, 22) table of
+        plane numbers (-1 in the columns of a field not in use).  Reads one file header for the plane size; touches no device.
+        Sets ``files`` [(path, first plane, channels)], ``planes``, ``hw``, ``plane_table`` (host) and ``needed_bytes``."""
+        fields = tuple(self.gpu_fields)
+        N = len(self)
+        table = np.full((N, COLS), -1, dtype=np.int64)
+        files, where = [], {}
+
+        def plane_of(path, channels):
+            p = where.get(path)
+            if p is None:
+                p = where[path] = (files[-1][1] + files[-1][2]) if files else 0
+                files.append((path, p, channels))
+            return p
+        for i in range(N):
+            paths = self._files(i)
+            if 'image' in fields:
+                table[i, 0] = plane_of(paths[0], 3)
+        for i in range(N):
+            if 'flow' in fields:
+                for j, path in enumerate(self._files(i)[1:21]):
+                    table[i, 1 + j] = plane_of(path, 1)
+        for i in range(N):
+            if 'gt' in fields:
+                table[i, 21] = plane_of(self._files(i)[21], 1)
+        if not files:
+            raise RuntimeError("ResidentSTDataset.plan: no files (an empty dataset or no field in gpu_fields)")
+        self.files = files
+        self.planes = files[-1][1] + files[-1][2]
+        self.hw = self._size_of(files[0][0], files[0][2])
+        self.plane_table = torch.from_numpy(table)
+        self.needed_bytes = self.planes * self.hw[0] * self.hw[1] + table.nbytes
+        self._plan = fields
+        return self
+
+    @staticmethod
+    def _read(path):
+        try:
+            with open(path, 'rb') as f:
+                return f.read()
+        except OSError as e:
+            raise RuntimeError(f"{path}: unreadable: {e}") from e
+
+    def _size_of(self, path, channels):
+        size = sniff(self._read(path))
+        return tuple(size) if size is not None else tuple(self._host_decode(path, channels).shape[1:])
+
+    @staticmethod
+    def _host_decode(path, channels):
+        try:
+            a = imread(path, gray=channels == 1)
+        except Exception as e:
+            raise RuntimeError(f"{path}: unreadable: {e}") from e
+        return a[None] if a.ndim == 2 else a.transpose((2, 0, 1))
+
+    # ------------------------------------------------------------------ fill (decode once)
+    def fill(self, device, budget_bytes=None, chunk=704):
+        """Decodes every distinct file once, ``chunk`` files at a time, straight into its planes of the pool on ``device``.
+        ``budget_bytes`` None: 0.8 x the free device memory.  A pool that does not fit raises before anything is allocated
+        (there is no partial cache).  Corrupt data warns, naming the file; an unsupported, unreadable or wrongly sized file
+        raises, naming it.  Prints the number of files, the bytes and the seconds once."""
+        if self._plan != tuple(self.gpu_fields):
+            self.plan()
+        device = torch.device(device)
+        if budget_bytes is None:
+            budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
+        if self.needed_bytes > budget_bytes:
+            raise RuntimeError(f"ResidentSTDataset.fill: the decoded dataset needs {self.needed_bytes} bytes "
+                               f"({self.planes} planes of {self.hw[0]} x {self.hw[1]}), {budget_bytes} bytes are allowed: "
+                               "run without --gpu_resident (there is no partial cache)")
+        from .. import hipops as H
+        t0 = time.perf_counter()
+        h, w = self.hw
+        pool = torch.empty((self.planes, h, w), dtype=torch.uint8, device=device)
+        stage = torch.empty((min(chunk, len(self.files)) * 3, h, w), dtype=torch.uint8, pin_memory=True)
+        pending = []                        # (host status words, event, paths) of the decode launches in flight
+        for c0 in range(0, len(self.files), chunk):
+            streams, offs, planes, chans, paths, host_idx, n_host = [], [0], [], [], [], [], 0
+            if pending:                     # the staging buffer is reused: the chunk before has left it
+                pending[-1][1].synchronize()
+            for path, plane, channels in self.files[c0:c0 + chunk]:
+                data = self._read(path) if self.decode == 'gpu' else None
+                size = sniff(data) if data is not None else None
+                if size is not None:
+                    streams.append(data)
+                    offs.append(offs[-1] + len(data))
+                    planes.append(plane)
+                    chans.append(channels)
+                    paths.append(path)
+                else:
+                    a = self._host_decode(path, channels)
+                    size = a.shape[1:]
+                    if tuple(size) == (h, w):
+                        stage[n_host:n_host + channels].copy_(torch.from_numpy(np.array(a)))
+                        host_idx.extend(range(plane, plane + channels))
+                        n_host += channels
+                if tuple(size) != (h, w):
+                    raise RuntimeError(f"{path}: {tuple(size)} pixels, the dataset's first file has {(h, w)}")
+            host = None
+            if streams:
+                blob = torch.frombuffer(bytearray(b"".join(streams)), dtype=torch.uint8).to(device)
+                _, status = H.jpeg_decode(blob, offs, (h, w), chans, out=pool, planes=planes, n3=sum(c == 3 for c in chans))
+                host = torch.empty(len(streams), dtype=torch.int32, pin_memory=True)
+                host.copy_(status, non_blocking=True)
+            if n_host:
+                pool.index_copy_(0, torch.tensor(host_idx, dtype=torch.int64).to(device, non_blocking=True),
+                                 stage[:n_host].to(device, non_blocking=True))
+            ev = torch.cuda.Event()
+            ev.record()
+            pending.append((host, ev, paths))
+        for host, ev, paths in pending:     # check_decode_status's rules
+            ev.synchronize()
+            if host is None:
+                continue
+            for i in torch.nonzero(host).flatten().tolist():
+                st = int(host[i])
+                if st == 1:
+                    warnings.warn(f"{paths[i]}: {H.JPEG_STATUS[1]} (decoded with zero padding, as libjpeg does)", RuntimeWarning)
+                else:
+                    raise RuntimeError(f"{paths[i]}: GPU JPEG decode failed: {H.JPEG_STATUS.get(st, st)}")
+        self.table = self.plane_table.to(device)
+        torch.cuda.synchronize(device)      # the gathers run on other streams (staged_batches' copy stream)
+        self.pool = pool
+        self.fill_seconds = time.perf_counter() - t0
+        print(f"resident dataset: {len(self.files)} files decoded ({self.decode}) into {self.planes} planes, "
+              f"{self.needed_bytes} bytes on {device}, {self.fill_seconds:.2f} s")
+        return self
+
+    # ------------------------------------------------------------------ samples
+    def __getitem__(self, index):
+        return {'index': index, 'fixsac': torch.FloatTensor([self.fixsac[index]]), 'imname': self.listTrainFiles[index]}
+
+    def _collate(self, batch):
+        return {'resident': self, 'index': torch.LongTensor([s['index'] for s in batch]),
+                'fixsac': torch.stack([s['fixsac'] for s in batch]), 'imname': [s['imname'] for s in batch]}
+
+    def gather(self, sample, device, fields=None, raw=False, prepare=True):
+        """The collated ``sample`` as device tensors: ``index`` crosses PCIe (non-blocking), one gather launch follows on the
+        current stream; its status word is left on ``sample`` for check_decode_status.  -> hipops.resident_gather's result."""
+        from .. import hipops as H
+        if self.pool is None:
+            raise RuntimeError("ResidentSTDataset: fill(device) has not run (the pool is not on the device)")
+        if torch.device(device) != self.pool.device:
+            raise RuntimeError(f"ResidentSTDataset: the pool is on {self.pool.device}, the batch is asked for on {device}")
+        fields = tuple(self.gpu_fields) if fields is None else tuple(fields)
+        missing = [f for f in fields if f not in self._plan]
+        if missing:
+            raise RuntimeError(f"ResidentSTDataset: field(s) {missing} were not in gpu_fields when the pool was filled")
+        idx = sample['index'].to(self.pool.device, non_blocking=True)
+        return H.resident_gather(self.pool, self.table, idx, fields=fields, raw=raw, prepare=prepare, status_to=sample)
+
+
+def fill_all(datasets, device, budget_gb=None):
+    """Fills several resident datasets (the training and the validation set of a script) under ONE budget: ``budget_gb``
+    GB, or 0.8 x the free memory of ``device``.  All are planned first, so a set that does not fit raises before any pool is
+    allocated."""
+    datasets = [ds for ds in datasets if len(ds)]
+    for ds in datasets:
+        ds.plan()
+    budget = int(budget_gb * 1e9) if budget_gb is not None else int(0.8 * torch.cuda.mem_get_info(torch.device(device))[0])
+    needed = sum(ds.needed_bytes for ds in datasets)
+    if needed > budget:
+        raise RuntimeError(f"--gpu_resident: the decoded datasets need {needed} bytes, {budget} bytes are allowed: "
+                           "run without --gpu_resident (there is no partial cache)")
+    for ds in datasets:
+        ds.fill(device, budget_bytes=budget)
+        budget -= ds.needed_bytes

@@ -136,7 +136,7 @@ def extractw(loader, model, savepath, crop_size=3, device='0', align=False, shar
         for i, sample in enumerate(loader):
             if not second(sample['fixsac']):
                 continue
-            if 'jpeg_blob' in sample:          # decode='gpu': the host path's normalised fields, decoded on the device
+            if 'jpeg_blob' in sample or 'resident' in sample:     # decode='gpu' / resident pool: the host path's normalised fields, made on the device
                 from .data.STdatas import check_decode_status, stage_batch
                 image, _, gt = stage_batch(sample, dev)
                 check_decode_status(sample)
@@ -156,7 +156,7 @@ def extract_LSTM_training_data(save_path='../512w', trained_model='save/best_fus
     model.load_state_dict(own)
     model.to(torch.device('cuda:' + device)).eval()
     for data, sub in ((traindata, 'train'), (valdata, 'test')):
-        loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
+        loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
                             collate_fn=getattr(data, 'collate_fn', None))
         extractw(loader, model, os.path.join(save_path, sub), crop_size, device, align, shard=shard)
     print('Attention weight for training LSTMnet successfully extracted.')

@@ -52,6 +52,12 @@ def build_parser():
     # not a reference flag: absent from the namespace unless given, so the parsed defaults stay the reference's 37
     a('--gpu_decode', action='store_true', default=argparse.SUPPRESS,
       help="decode the dataset's JPEGs on the GPU (STDataset(decode='gpu')); default: host decode as the reference")
+    a('--gpu_resident', action='store_true', default=argparse.SUPPRESS,
+      help="decode every file once and keep the planes in device memory (data.resident); batches are gathered on the GPU. "
+           "With --gpu_decode the one-time fill decodes on the GPU")
+    a('--gpu_resident_gb', type=float, default=argparse.SUPPRESS,
+      help='device memory the resident dataset may take, in GB, shared by the training and validation sets '
+           '(default: 0.8 x what is free)')
     return p
 
 
@@ -73,7 +79,8 @@ def _at_stage(args, STTrainData, STValData):
         if not args.train_lstm:
             att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data in (STValData, STTrainData):
-            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
+            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False,
+                                        num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
                                         collate_fn=getattr(data, 'collate_fn', None)),
                              args.extract_late_pred_folder, args.extract_late_feat_folder)
 
@@ -103,7 +110,8 @@ def _at_stage_sharded(args, STTrainData, STValData):
         # every rank runs the whole recurrence of extract_late: all of them take the weights from the one saved file
         att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data in (STValData, STTrainData):
-            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=1, pin_memory=True,
+            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False,
+                                        num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
                                         collate_fn=getattr(data, 'collate_fn', None)),
                              args.extract_late_pred_folder, args.extract_late_feat_folder, shard=shard)
     dp.barrier()                          # LF lists the folders: not before every rank has written its files
@@ -152,10 +160,15 @@ def main(argv=None):
     listTrainFiles, listValFiles = _split(args.imagePath, args.val_name)
     print('num of val samples: ', len(listValFiles))
     decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
+    resident = getattr(args, 'gpu_resident', False)
+    if resident:                            # the planes live on the device; batches are gathered there (data/resident.py)
+        from .data.resident import ResidentSTDataset as STDataset, fill_all
     STTrainData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listTrainFiles, listGtFiles,
                             listfixsacTrain, args.fixsacPath, raw_u8=True, decode=decode)   # bytes over PCIe, normalised on the GPU
     STValData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
                           listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
+    if resident:
+        fill_all((STTrainData, STValData), torch.device('cuda:' + args.device), getattr(args, 'gpu_resident_gb', None))
     os.makedirs(args.save_path, exist_ok=True)
     if args.train_sp:
         sp = SP(lr=args.lr, loss_save=args.sp_save_img, save_name=args.save_sp, save_path=args.save_path,

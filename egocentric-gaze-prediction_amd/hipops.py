@@ -1316,6 +1316,9 @@ def prepare_network_input(x: torch.Tensor, Cp: int = 32):
     (~0.14 ms at batch 32) out of the serial head of the forward pass and under the MFMA-bound kernels of the step before.  The
     prepared tensor rides on ``x`` and is consumed ONCE by functions.ConvBNReLUPool (the tensor's version and shape are
     checked; anything else falls back to the in-step conversion)."""
+    prep = getattr(x, "_egz_prepared", None)
+    if prep is not None and prep[1] == x._version and prep[0].shape[3] == Cp:
+        return prep[0]                     # the producer of x wrote it already (resident_gather)
     if not (x.is_cuda and x.dim() == 4 and 16 <= x.shape[1] <= Cp and PRECISION == "split" and x.is_contiguous()):
         return None
     xin = nchw_to_nhwc_pad(x.detach(), Cp)
@@ -2119,6 +2122,87 @@ def u8_normalize(src: torch.Tensor, mean, std) -> torch.Tensor:
     check(LIB.egz_u8_normalize(src.data_ptr(), dst.data_ptr(), src.numel(), plane, C, hit[0].data_ptr(),
                                hit[1].data_ptr(), _stream()), "egz_u8_normalize")
     return dst
+
+
+# ----------------------------------------------------------------------------- resident dataset (data/resident.py, --gpu_resident)
+RESIDENT_STATUS = {1: "a sample number (idx) outside the table", 2: "a plane-table entry outside the pool",
+                   3: "a sample number outside the table and a plane-table entry outside the pool"}
+_RESIDENT_FIELDS = {'image': 1, 'flow': 2, 'gt': 4}
+
+
+def check_resident_status(pending) -> None:
+    """Waits for the gather that ``pending = (host status word, event)`` belongs to and raises if it skipped a sample."""
+    host, ev = pending
+    ev.synchronize()
+    st = int(host[0])
+    if st:
+        raise RuntimeError(f"resident_gather: {RESIDENT_STATUS.get(st, st)}: the sample was skipped, its outputs are undefined")
+
+
+def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, fields=('image', 'flow', 'gt'),
+                    raw: bool = False, prepare: bool = True, status_to: Optional[dict] = None):
+    """A batch of the SP / AT sample layout gathered from a pool of decoded planes on the device (egz_resident_gather).
+
+    pool: uint8 (P, H, W); table: int64 (N, 22) plane numbers (column 0 the first of 3 BGR planes, 1 .. 20 the flow planes in
+    STdatas order, 21 the ground truth); idx: int64 (B,) sample numbers; all on the GPU.  -> ``(image, flow, gt)`` fp32
+    (B,3,H,W) / (B,20,H,W) / (B,1,H,W), normalised as data.STdatas.stage_batch does (bit-identical), None for a field not in
+    ``fields``; with ``raw=True`` instead the uint8 (B,24,H,W) bytes (image 0:3, flow 3:23, gt 23; planes of fields not in
+    ``fields`` are not written).  Under the conditions of prepare_network_input the flow stack's NHWC-32 form and its abs-max
+    come out of the same launch and ride on ``flow`` (``flow._egz_prepared``).  An index out of range is never dereferenced:
+    the status word is read here (a wait for this launch), or, with ``status_to`` (a dict, e.g. the collated sample), left
+    there under '_resident_status' for check_resident_status at hand-over."""
+    from .data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
+            and pool.is_contiguous()):
+        raise ValueError("resident_gather: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
+    dev = pool.device
+    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 22
+            and table.is_contiguous()):
+        raise ValueError("resident_gather: table must be a contiguous int64 (N, 22) tensor on the pool's device")
+    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
+        raise ValueError("resident_gather: idx must be a contiguous int64 (B,) tensor on the pool's device")
+    fields = tuple(fields)
+    if not fields or any(f not in _RESIDENT_FIELDS for f in fields):
+        raise ValueError(f"resident_gather: fields {fields!r} must name some of 'image', 'flow', 'gt'")
+    P, H, W = pool.shape
+    B = idx.numel()
+    key = ('resident', dev.index or 0)
+    const = _NORM_CONST.get(key)
+    if const is None:
+        const = (torch.tensor(IMAGE_MEAN + FLOW_MEAN + (0.0,), dtype=torch.float32, device=dev),
+                 torch.tensor(IMAGE_STD + FLOW_STD + (1.0,), dtype=torch.float32, device=dev))
+        _NORM_CONST[key] = const
+    new = lambda C: torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    image = flow = gt = xin = am = out_raw = None
+    if raw:
+        out_raw = torch.empty((B, 24, H, W), dtype=torch.uint8, device=dev)
+    else:
+        image = new(3) if 'image' in fields else None
+        flow = new(20) if 'flow' in fields else None
+        gt = new(1) if 'gt' in fields else None
+        if flow is not None and prepare and PRECISION == "split":
+            xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
+            am = _new_absmax(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_resident_gather(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
+                                  const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin), _p(am),
+                                  _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)), status.data_ptr(), _stream()),
+          "egz_resident_gather")
+    if xin is not None:
+        if _want_fwd_absmax():
+            xin._egz_absmax = am
+        ev = torch.cuda.Event()
+        ev.record()
+        flow._egz_prepared = (xin, flow._version, ev)
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_resident_status'] = (host, done)
+    else:
+        check_resident_status((host, done))
+    return out_raw if raw else (image, flow, gt)
 
 
 def crop_mean(feat_nhwc: torch.Tensor, gp, size: int, cell: int = 16) -> torch.Tensor:

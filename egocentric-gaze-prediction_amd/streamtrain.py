@@ -101,6 +101,9 @@ def stage_stream(sample, device, key, prepare=True):
     NHWC-32 re-layout is issued behind the copy (hipops.prepare_network_input), as data.STdatas.stage_batch does for SP."""
     from . import hipops as H
     from .data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
+    if 'resident' in sample:                   # data.resident: gathered from the pool on the device, NHWC-32 form included
+        got = sample['resident'].gather(sample, device, fields=(key, 'gt'), prepare=prepare)
+        return got[0 if key == 'image' else 1], got[2]
     if 'jpeg_blob' in sample:                  # decode='gpu': decoded on the device into the raw_u8 layout
         from .data.STdatas import decode_to_u8
         image, flow, gt = decode_to_u8(sample, device)
@@ -255,6 +258,12 @@ def build_parser(stream):
     # absent from the namespace unless given: the parsed defaults stay the reference's
     p.add_argument('--gpu_decode', action='store_true', default=argparse.SUPPRESS,
                    help="decode the dataset's JPEGs on the GPU (STDataset(decode='gpu')); default: host decode as the reference")
+    p.add_argument('--gpu_resident', action='store_true', default=argparse.SUPPRESS,
+                   help="decode every file once and keep the planes in device memory (data.resident); batches are gathered on "
+                        "the GPU.  With --gpu_decode the one-time fill decodes on the GPU")
+    p.add_argument('--gpu_resident_gb', type=float, default=argparse.SUPPRESS,
+                   help='device memory the resident dataset may take, in GB, shared by the training and validation sets '
+                        '(default: 0.8 x what is free)')
     return p
 
 
@@ -292,18 +301,25 @@ def make_loaders(args, key=None):
     listValFiles = sorted(k for k in os.listdir(args.imagePath) if args.val_name in k)
     print('num of val samples: ', len(listValFiles))
     decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
+    resident = getattr(args, 'gpu_resident', False)
+    if resident:                            # the planes live on the device; batches are gathered there (data/resident.py)
+        from .data.resident import ResidentSTDataset as STDataset, fill_all
     train_data = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listTrainFiles, listGtFiles,
                            listfixsacTrain, args.fixsacPath, raw_u8=True, decode=decode)   # bytes over PCIe, normalised on the GPU
     val_data = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
                          listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
     if key is not None:                    # decode='gpu': only the stream's input and the ground truth are read and decoded
         train_data.gpu_fields = val_data.gpu_fields = (key, 'gt')
+    if resident:
+        fill_all((train_data, val_data), torch.device('cuda:' + str(args.device)), getattr(args, 'gpu_resident_gb', None))
     train_sampler = dp.RankShardSampler(train_data, True, args.batch_size) if dp.world_size() > 1 else None
     val_sampler = dp.RankShardSampler(val_data, False, args.batch_size, pad=False) if dp.world_size() > 1 else None
     train_loader = DataLoader(dataset=train_data, batch_size=args.batch_size, shuffle=train_sampler is None,
-                              sampler=train_sampler, num_workers=0, pin_memory=True, collate_fn=train_data.collate_fn)
-    val_loader = DataLoader(dataset=val_data, batch_size=args.batch_size, shuffle=False, sampler=val_sampler, num_workers=0,
-                            pin_memory=True, collate_fn=val_data.collate_fn)
+                              sampler=train_sampler, num_workers=getattr(train_data, 'loader_workers', 0), pin_memory=True,
+                              collate_fn=train_data.collate_fn)
+    val_loader = DataLoader(dataset=val_data, batch_size=args.batch_size, shuffle=False, sampler=val_sampler,
+                            num_workers=getattr(val_data, 'loader_workers', 0), pin_memory=True,
+                            collate_fn=val_data.collate_fn)
     return train_loader, val_loader, train_sampler
 
 

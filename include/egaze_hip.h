@@ -453,6 +453,19 @@ int egz_cat2_planes(const float* f, const float* g, float* out, int B, long HW, 
  * (u8 / 255 - mean[c]) / std[c] in fp32, the reference's three correctly-rounded operations (bit-exact). */
 int egz_u8_normalize(const unsigned char* src, float* dst, long n, long plane, int C, const float* mean,
                      const float* std, hipStream_t stream);
+/* A batch gathered from a pool of decoded planes that stays on the device (data/resident.py, csrc/batch_gather.hip).  pool
+ * (P, H, W) uint8; table (N, 22) int64 plane numbers per sample -- column 0 the first of 3 consecutive BGR planes, 1 .. 20 the
+ * flow planes (x_t, y_t, x_{t-1}, y_{t-1}, ...), 21 the ground truth; idx (B,) int64 sample numbers; mean / std 24 floats each.
+ * Outputs, each optional (null: not produced, nothing written): image (B,3,H,W), flow (B,20,H,W), gt (B,1,H,W) fp32 =
+ * (u8 / 255 - mean) / std, bit-identical with egz_u8_normalize of the gathered bytes; flow_nhwc32 (B,H,W,32), bit-identical
+ * with egz_nchw_to_nhwc_pad of flow (channels 20 .. 31 zero), together with absmax (egz_absmax layout, zero-filled by the
+ * caller: receives max |flow|); raw (B,24,H,W) uint8, the gathered bytes, of which the fields in raw_fields (bit 0 image, 1
+ * flow, 2 gt) are written.  H * W % 4 == 0; pool offsets are 64-bit.  A sample number or a table entry of a field in use that is
+ * out of range is not dereferenced: that sample is skipped and *status (device, zero-filled by the caller) gets bit 0 (idx)
+ * or bit 1 (table). */
+int egz_resident_gather(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H, int W,
+                        const float* mean, const float* std, float* image, float* flow, float* gt, float* flow_nhwc32,
+                        unsigned int* absmax, unsigned char* raw, int raw_fields, int* status, hipStream_t stream);
 /* AT extraction glue (AT.py:25-39,58-66,229; extractLSTMw.py:81-90): chn_weight = mean of the size x size window of the
  * channels-last (B,H,W,C) feature map around gaze_point / cell; weighted map = min-max normalised sum_c feat * w. */
 int egz_crop_mean(const float* feat, const int* gp, float* out, int B, int H, int W, int C, int size, int cell,
