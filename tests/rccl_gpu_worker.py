@@ -4,7 +4,9 @@ A 1-rank all-reduce is legal and runs exactly the code path the 8-GPU job runs p
 the gradient sinks during backward, every bucket is issued as an ASYNC RCCL all-reduce from the comm stream (which waits
 for all producer streams), and FusedAdam.step() joins the handles before the Adam kernel.  gloo -- the backend of every
 other DP test -- stages device tensors through the host and synchronises, so none of that ordering is exercised there.
-Writes its observations as JSON to argv[1]."""
+Writes its observations as JSON to argv[1].  With argv[5] / argv[6] (stream configurations, delay in ms) it also repeats
+two training steps under each of them and adds their digests (step (3) below)."""
+import hashlib
 import json
 import os
 import sys
@@ -88,6 +90,35 @@ def main():
            "grad_bit_exact": bool(torch.equal(g_ref, g_rccl)), "grad_absmax": float(g_ref.abs().max()),
            "params_bit_exact": bool(torch.equal(p_ref, p_rccl)), "params_moved": bool(not torch.equal(p_ref, p0)),
            "steps_joined": red.stats["steps"], "backend": dist.get_backend(), "world": dist.get_world_size()}
+
+    # (3) opt-in (argv[5] = comma-separated configurations, argv[6] = delay in ms; tests/test_hip_stream_order.py): two more
+    # training steps with the reducer attached per configuration -- 'serial' (stream concurrency off: the oracle) or a mode of
+    # stream_perturb.perturb -- from the same initial state, fresh inputs each step, freed memory poisoned; a digest of the
+    # reduced gradients, the loss and the parameters after each step (read in stream order, no host wait in between)
+    if len(sys.argv) > 5:
+        from stream_perturb import perturb, poison, serial
+
+        def digest(t):
+            return hashlib.sha256(t.detach().cpu().reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()
+        obs["digests"] = {}
+        for config in sys.argv[5].split(","):
+            restore()
+            torch.cuda.synchronize()
+            kept = []
+            with (serial() if config == "serial" else perturb(config, float(sys.argv[6]))):
+                for s in range(2):
+                    poison(H)
+                    fresh = synthetic.sp_batch(batch, size, dev, seed=200 + s)
+                    opt.zero_grad()
+                    out = model(fresh["image"], fresh["flow"])
+                    loss = crit(out, fresh["gt"].view(out.size()))
+                    loss.backward()
+                    opt.step()                     # (its pre-step hook is the reducer's wait())
+                    kept += [(f"step {s}/reduced gradients", opt.flat_g.clone()), (f"step {s}/loss", loss.detach().clone()),
+                             (f"step {s}/parameters", opt.flat_p.clone())]
+                    del fresh, out, loss
+                torch.cuda.synchronize()
+            obs["digests"][config] = [(k, digest(t)) for k, t in kept]
     with open(out_path, "w") as f:
         json.dump(obs, f)
     dist.destroy_process_group()

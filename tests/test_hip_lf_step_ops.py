@@ -28,6 +28,7 @@ import torch
 
 from oracle import egaze_oracle as O
 from oracle import synth
+from stream_perturb import poison
 
 pytestmark = pytest.mark.gpu
 
@@ -215,20 +216,6 @@ TRACKED = ("cat2_planes", "conv_first_fwd", "conv3x3_fwd", "bn_finalize", "bn_fi
            "conv1x1_sigmoid_bwd_masked", "bn_relu_pool_bwd", "conv3x3_dgrad_bnsums", "conv3x3_dgrad", "conv3x3_wgrad",
            "bn_bwd_first_wgrad", "conv_first_wgrad", "channel_stats", "relu_bwd_bias")
 INPLACE = ("running_mean", "running_var", "num_batches_tracked")
-
-
-def poison(h):
-    """Fill every hipops workspace and a spread of freed caching-allocator blocks with 0xFF bytes (NaN in fp32 and fp64), so that
-    a row / tile a kernel forgets to write reads back as NaN rather than as a lucky zero."""
-    torch.cuda.synchronize()
-    for ws in h._WS.values():
-        ws.fill_(255)
-    junk = [torch.empty(256 << 20, dtype=torch.uint8, device=DEV)]
-    junk += [torch.empty(n, dtype=torch.uint8, device=DEV) for n in [1 << 20] * 8 + [64 << 10] * 16 + [4096] * 64 + [512] * 64]
-    for t in junk:
-        t.fill_(255)
-    torch.cuda.synchronize()
-    del junk
 
 
 class Recorder:
