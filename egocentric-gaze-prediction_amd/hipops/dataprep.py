@@ -1,0 +1,283 @@
+"""Dataset preparation and input pipeline: gaze maps, u8 normalise, the resident gather, AT glue."""
+from __future__ import annotations
+
+import sys
+from typing import Optional
+
+import torch
+
+from .._lib import check
+from ._core import LIB, _p, _req, _stream
+from .absmax import _new_absmax, _want_fwd_absmax
+from .metrics import _gauss_weights
+
+_H = sys.modules[__package__]      # the package: switches and public functions are read through it at call time
+
+
+# ----------------------------------------------------------------------------- dataset preparation (ground-truth gaze maps)
+def area_table(ssize: int, dsize: int):
+    """OpenCV's INTER_AREA decimation table for one axis, non-integer scale (computeResizeAreaTab in imgproc/resize.cpp,
+    restated here: cv2 is not a dependency of this package).  -> (ofs int32 [dsize + 1], si int32 [K], alpha float32 [K]):
+    the entries of output index d are [ofs[d], ofs[d + 1]), in OpenCV's order."""
+    import math
+    import numpy as np
+    if not (0 < dsize <= ssize):
+        raise ValueError(f"area_table: INTER_AREA decimation needs 0 < dsize <= ssize (got {ssize} -> {dsize})")
+    scale = 1.0 / (dsize / ssize)
+    ofs, si, alpha = [0], [], []
+    for d in range(dsize):
+        fs1 = d * scale
+        fs2 = fs1 + scale
+        cell = min(scale, ssize - fs1)
+        s1, s2 = math.ceil(fs1), math.floor(fs2)
+        s2 = min(s2, ssize - 1)
+        s1 = min(s1, s2)
+        if s1 - fs1 > 1e-3:
+            si.append(s1 - 1); alpha.append((s1 - fs1) / cell)
+        for s in range(s1, s2):
+            si.append(s); alpha.append(1.0 / cell)
+        if fs2 - s2 > 1e-3:
+            si.append(s2); alpha.append(min(min(fs2 - s2, 1.0), cell) / cell)
+        ofs.append(len(si))
+    return np.array(ofs, np.int32), np.array(si, np.int32), np.array(alpha, np.float32)
+
+
+_AREA_T = {}
+
+
+def _area_tables(device, src_hw, out_hw):
+    key = (torch.device(device).index or 0, tuple(src_hw), tuple(out_hw))
+    hit = _AREA_T.get(key)
+    if hit is None:
+        hit = tuple(tuple(torch.from_numpy(a).to(device) for a in _H.area_table(s, d)) for s, d in zip(src_hw, out_hw))
+        _AREA_T[key] = hit
+    return hit          # ((y ofs, si, alpha), (x ofs, si, alpha))
+
+
+def gaze_gt_maps(rows: torch.Tensor, cols: torch.Tensor, src_hw, sigma: float, out_hw=(224, 224), mode: int = 0,
+                 want_f64: bool = False, want_fullres: bool = False):
+    """Ground-truth gaze maps of the reference's dataset preparation, N frames in one launch (egz_gaze_gt_maps).
+
+    rows, cols: (N,) integer tensors on the GPU, the impulse position of each frame in [0, H) x [0, W) (negative indices
+    already wrapped).  Each map is scipy.ndimage.gaussian_filter(impulse, sigma) over src_hw = (H, W), min-max normalised,
+    times 255 and area-resized to out_hw: mode 0 resizes the float64 map and rounds (data/dataset_preprocessing.py, GTEA
+    Gaze+, cv2.imwrite of a float64 image), mode 1 truncates to uint8 first and resizes with float accumulation
+    (misc/gazedataset_gt.py, GTEA Gaze).  -> (u8 (N, oh, ow), f64 (N, oh, ow) or None, fullres (N, H, W) float64 or None),
+    all on the GPU; the full-resolution maps cost 8 H W bytes each (tests)."""
+    for t, name in ((rows, "rows"), (cols, "cols")):
+        if not t.is_cuda:
+            raise RuntimeError(f"gaze_gt_maps: {name}: expected a HIP ('cuda') tensor -- this package has no CPU path")
+        if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool or t.dim() != 1:
+            raise ValueError(f"gaze_gt_maps: {name} must be a 1-D integer tensor, got {t.dtype} {tuple(t.shape)}")
+    if rows.numel() != cols.numel() or rows.numel() == 0 or rows.device != cols.device:
+        raise ValueError(f"gaze_gt_maps: rows / cols must be non-empty, of one length and on one device "
+                         f"({rows.numel()} vs {cols.numel()})")
+    H, W = (int(v) for v in src_hw)
+    oh, ow = (int(v) for v in out_hw)
+    if mode not in (0, 1):
+        raise ValueError(f"gaze_gt_maps: mode {mode} is neither 0 (GTEA Gaze+) nor 1 (GTEA Gaze)")
+    if not (0 < oh <= H and 0 < ow <= W):
+        raise ValueError(f"gaze_gt_maps: INTER_AREA decimation needs 0 < out <= src (got {(H, W)} -> {(oh, ow)})")
+    if not sigma > 0:
+        raise ValueError(f"gaze_gt_maps: sigma must be positive, got {sigma}")
+    dev = rows.device
+    gw, radius = _gauss_weights(dev, float(sigma))
+    if radius >= min(H, W):
+        raise ValueError(f"gaze_gt_maps: kernel radius {radius} (sigma {sigma}) must be below min(H, W) = {min(H, W)}")
+    pos = torch.stack((rows.to(torch.int64), cols.to(dev, torch.int64)), 1)
+    bad = ((pos[:, 0] < 0) | (pos[:, 0] >= H) | (pos[:, 1] < 0) | (pos[:, 1] >= W)).any()
+    if bool(bad):
+        raise ValueError(f"gaze_gt_maps: impulse positions must lie in [0, {H}) x [0, {W})")
+    pos = pos.to(torch.int32).contiguous()
+    (yo, ys, ya), (xo, xs, xa) = _area_tables(dev, (H, W), (oh, ow))
+    N = pos.shape[0]
+    u8 = torch.empty((N, oh, ow), dtype=torch.uint8, device=dev)
+    f64 = torch.empty((N, oh, ow), dtype=torch.float64, device=dev) if want_f64 else None
+    full = torch.empty((N, H, W), dtype=torch.float64, device=dev) if want_fullres else None
+    check(LIB.egz_gaze_gt_maps(pos.data_ptr(), N, H, W, gw.data_ptr(), radius, xo.data_ptr(), xs.data_ptr(), xa.data_ptr(),
+                               xs.numel(), yo.data_ptr(), ys.data_ptr(), ya.data_ptr(), ys.numel(), mode, oh, ow,
+                               u8.data_ptr(), f64.data_ptr() if f64 is not None else None,
+                               full.data_ptr() if full is not None else None, _stream()), "egz_gaze_gt_maps")
+    return u8, f64, full
+
+
+# ----------------------------------------------------------------------------- input pipeline / AT glue
+_NORM_CONST = {}
+
+
+def u8_normalize(src: torch.Tensor, mean, std) -> torch.Tensor:
+    """src: uint8 (..., C, H, W) on the GPU -> fp32 (u8 / 255 - mean[c]) / std[c] (bit-exact with the torch expression)."""
+    if src.dtype != torch.uint8 or not src.is_cuda or not src.is_contiguous():
+        raise ValueError("u8_normalize: contiguous CUDA uint8 tensor expected")
+    C, plane = src.shape[-3], src.shape[-2] * src.shape[-1]
+    key = (src.device.index or 0, tuple(float(v) for v in mean), tuple(float(v) for v in std))
+    hit = _NORM_CONST.get(key)
+    if hit is None:
+        hit = (torch.tensor(key[1], dtype=torch.float32, device=src.device),
+               torch.tensor(key[2], dtype=torch.float32, device=src.device))
+        _NORM_CONST[key] = hit
+    if hit[0].numel() != C:
+        raise ValueError(f"u8_normalize: {C} channels but {hit[0].numel()} mean / std values")
+    dst = torch.empty(src.shape, dtype=torch.float32, device=src.device)
+    check(LIB.egz_u8_normalize(src.data_ptr(), dst.data_ptr(), src.numel(), plane, C, hit[0].data_ptr(),
+                               hit[1].data_ptr(), _stream()), "egz_u8_normalize")
+    return dst
+
+
+# ----------------------------------------------------------------------------- resident dataset (data/resident.py, --gpu_resident)
+RESIDENT_STATUS = {1: "a sample number (idx) outside the table", 2: "a plane-table entry outside the pool",
+                   3: "a sample number outside the table and a plane-table entry outside the pool"}
+_RESIDENT_FIELDS = {'image': 1, 'flow': 2, 'gt': 4}
+
+
+def check_resident_status(pending) -> None:
+    """Waits for the gather that ``pending = (host status word, event)`` belongs to and raises if it skipped a sample."""
+    host, ev = pending
+    ev.synchronize()
+    st = int(host[0])
+    if st:
+        raise RuntimeError(f"resident_gather: {RESIDENT_STATUS.get(st, st)}: the sample was skipped, its outputs are undefined")
+
+
+def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, fields=('image', 'flow', 'gt'),
+                    raw: bool = False, prepare: bool = True, status_to: Optional[dict] = None):
+    """A batch of the SP / AT sample layout gathered from a pool of decoded planes on the device (egz_resident_gather).
+
+    pool: uint8 (P, H, W); table: int64 (N, 22) plane numbers (column 0 the first of 3 BGR planes, 1 .. 20 the flow planes in
+    STdatas order, 21 the ground truth); idx: int64 (B,) sample numbers; all on the GPU.  -> ``(image, flow, gt)`` fp32
+    (B,3,H,W) / (B,20,H,W) / (B,1,H,W), normalised as data.STdatas.stage_batch does (bit-identical), None for a field not in
+    ``fields``; with ``raw=True`` instead the uint8 (B,24,H,W) bytes (image 0:3, flow 3:23, gt 23; planes of fields not in
+    ``fields`` are not written).  Under the conditions of prepare_network_input the flow stack's NHWC-32 form and its abs-max
+    come out of the same launch and ride on ``flow`` (``flow._egz_prepared``).  An index out of range is never dereferenced:
+    the status word is read here (a wait for this launch), or, with ``status_to`` (a dict, e.g. the collated sample), left
+    there under '_resident_status' for check_resident_status at hand-over."""
+    from ..data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
+            and pool.is_contiguous()):
+        raise ValueError("resident_gather: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
+    dev = pool.device
+    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 22
+            and table.is_contiguous()):
+        raise ValueError("resident_gather: table must be a contiguous int64 (N, 22) tensor on the pool's device")
+    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
+        raise ValueError("resident_gather: idx must be a contiguous int64 (B,) tensor on the pool's device")
+    fields = tuple(fields)
+    if not fields or any(f not in _RESIDENT_FIELDS for f in fields):
+        raise ValueError(f"resident_gather: fields {fields!r} must name some of 'image', 'flow', 'gt'")
+    P, H, W = pool.shape
+    B = idx.numel()
+    key = ('resident', dev.index or 0)
+    const = _NORM_CONST.get(key)
+    if const is None:
+        const = (torch.tensor(IMAGE_MEAN + FLOW_MEAN + (0.0,), dtype=torch.float32, device=dev),
+                 torch.tensor(IMAGE_STD + FLOW_STD + (1.0,), dtype=torch.float32, device=dev))
+        _NORM_CONST[key] = const
+    new = lambda C: torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    image = flow = gt = xin = am = out_raw = None
+    if raw:
+        out_raw = torch.empty((B, 24, H, W), dtype=torch.uint8, device=dev)
+    else:
+        image = new(3) if 'image' in fields else None
+        flow = new(20) if 'flow' in fields else None
+        gt = new(1) if 'gt' in fields else None
+        if flow is not None and prepare and _H.PRECISION == "split":
+            xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
+            am = _new_absmax(dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_resident_gather(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
+                                  const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin), _p(am),
+                                  _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)), status.data_ptr(), _stream()),
+          "egz_resident_gather")
+    if xin is not None:
+        if _want_fwd_absmax():
+            xin._egz_absmax = am
+        ev = torch.cuda.Event()
+        ev.record()
+        flow._egz_prepared = (xin, flow._version, ev)
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_resident_status'] = (host, done)
+    else:
+        _H.check_resident_status((host, done))
+    return out_raw if raw else (image, flow, gt)
+
+
+def crop_mean(feat_nhwc: torch.Tensor, gp, size: int, cell: int = 16) -> torch.Tensor:
+    """feat_nhwc: (B,H,W,C) fp32; gp: B gaze points (row, col) in input pixels -> chn_weight (B, C)."""
+    _req(feat_nhwc, "feature")
+    B, Hh, Ww, C = feat_nhwc.shape
+    if isinstance(gp, torch.Tensor) and gp.is_cuda and gp.dtype == torch.int32 and gp.is_contiguous() and gp.numel() == 2 * B:
+        g = gp                           # already on the device (u8_center_of_mass): no host round trip
+    else:
+        g = torch.as_tensor(gp, dtype=torch.int32).reshape(B, 2).to(feat_nhwc.device)
+    out = torch.empty((B, C), dtype=torch.float32, device=feat_nhwc.device)
+    check(LIB.egz_crop_mean(feat_nhwc.data_ptr(), g.data_ptr(), out.data_ptr(), B, Hh, Ww, C, int(size), int(cell),
+                            _stream()), "egz_crop_mean")
+    return out
+
+
+def window_mean(feat_nhwc: torch.Tensor, windows) -> torch.Tensor:
+    """feat_nhwc: (B,H,W,C) fp32; windows: B x (y0, y1, x0, x1) half-open cell ranges -> (B, C) window means."""
+    _req(feat_nhwc, "feature")
+    B, Hh, Ww, C = feat_nhwc.shape
+    win = [tuple(int(v) for v in w) for w in windows]
+    if len(win) != B or any(not (0 <= y0 < y1 <= Hh and 0 <= x0 < x1 <= Ww) for y0, y1, x0, x1 in win):
+        raise ValueError(f"window_mean: windows {win} do not fit a {Hh} x {Ww} map of batch {B}")
+    g = torch.tensor(win, dtype=torch.int32).to(feat_nhwc.device)
+    out = torch.empty((B, C), dtype=torch.float32, device=feat_nhwc.device)
+    check(LIB.egz_window_mean(feat_nhwc.data_ptr(), g.data_ptr(), out.data_ptr(), B, Hh, Ww, C, _stream()),
+          "egz_window_mean")
+    return out
+
+
+def pixel_weighted_sum(feat_nhwc: torch.Tensor, wmap) -> torch.Tensor:
+    """feat_nhwc: (B,H,W,C); wmap: (B,H,W) per-pixel weights (host array / tensor) -> (B, C) = sum_p wmap[p] * feat[p]."""
+    _req(feat_nhwc, "feature")
+    B, Hh, Ww, C = feat_nhwc.shape
+    wm = torch.as_tensor(wmap, dtype=torch.float32).reshape(B, Hh * Ww).contiguous().to(feat_nhwc.device)
+    out = torch.empty((B, C), dtype=torch.float32, device=feat_nhwc.device)
+    check(LIB.egz_pixel_weighted_sum(feat_nhwc.data_ptr(), wm.data_ptr(), out.data_ptr(), B, Hh * Ww, C, _stream()),
+          "egz_pixel_weighted_sum")
+    return out
+
+
+def weighted_minmax(feat_nhwc: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """feat_nhwc: (B,H,W,C), w: (B,C) -> (B,H,W): channel-weighted sum, min-max normalised per image."""
+    _req(feat_nhwc, "feature"); _req(w, "chn_weight")
+    B, Hh, Ww, C = feat_nhwc.shape
+    out = torch.empty((B, Hh, Ww), dtype=torch.float32, device=feat_nhwc.device)
+    check(LIB.egz_weighted_minmax(feat_nhwc.data_ptr(), w.data_ptr(), out.data_ptr(), B, Hh * Ww, C, _stream()),
+          "egz_weighted_minmax")
+    return out
+
+
+def u8_center_of_mass(maps: torch.Tensor, want_u8: bool = False):
+    """maps: (B, H, W) fp32 in [0, 1] -> (com (B, 2) float64, gp (B, 2) int32 = floor(com)[, q (B, H, W) uint8]): the
+    reference's ``ndimage.center_of_mass((map * 255).astype(np.uint8))`` (run_spatialstream.py:99-104,130-131), bit for bit."""
+    _req(maps, "map")
+    B, Hh, Ww = maps.shape
+    com = torch.empty((B, 2), dtype=torch.float64, device=maps.device)
+    gp = torch.empty((B, 2), dtype=torch.int32, device=maps.device)
+    q = torch.empty((B, Hh, Ww), dtype=torch.uint8, device=maps.device) if want_u8 else None
+    check(LIB.egz_u8_center_of_mass(maps.data_ptr(), B, Hh, Ww, com.data_ptr(), gp.data_ptr(), _p(q), _stream()),
+          "egz_u8_center_of_mass")
+    return (com, gp, q) if want_u8 else (com, gp)
+
+
+def bilinear_up(src: torch.Tensor, scale: int, align_corners: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """src: (B, h, w) -> (B, h*scale, w*scale), ``nn.functional.interpolate(mode='bilinear')`` with either align_corners
+    convention.  ``out``: a (B, H, W) destination whose samples may be strided (e.g. ``x[:, 1]`` of a (B, 2, H, W) tensor --
+    channel 1 of late_fusion's input) but whose rows are dense."""
+    _req(src, "src")
+    B, h, w = src.shape
+    Hh, Ww = h * scale, w * scale
+    if out is None:
+        out = torch.empty((B, Hh, Ww), dtype=torch.float32, device=src.device)
+    if tuple(out.shape) != (B, Hh, Ww) or out.dtype != torch.float32 or not out.is_cuda or out.stride(2) != 1 or out.stride(1) != Ww:
+        raise RuntimeError(f"bilinear_up: destination {tuple(out.shape)} / strides {out.stride()} does not fit {(B, Hh, Ww)}")
+    check(LIB.egz_bilinear_up(src.data_ptr(), out.data_ptr(), B, h, w, int(scale), int(bool(align_corners)),
+                              out.stride(0) if B > 1 else Hh * Ww, _stream()), "egz_bilinear_up")
+    return out

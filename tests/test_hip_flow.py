@@ -274,8 +274,12 @@ class _Recorder:
 def test_refusals_launch_nothing(monkeypatch):
     from egaze_amd import _lib
     from egaze_amd import hipops as H
+    import sys
     rec = _Recorder(H.LIB)
     monkeypatch.setattr(H, "LIB", rec)
+    for name, mod in list(sys.modules.items()):       # every family module binds the one proxy under its own name
+        if name.startswith(H.__name__ + ".") and getattr(mod, "LIB", None) is not None:
+            monkeypatch.setattr(mod, "LIB", rec)
     ok = torch.zeros((3, 32, 40), dtype=torch.uint8, device=DEV)
     with pytest.raises(RuntimeError, match="expected a HIP"):
         H.tvl1_flow(ok.cpu())
