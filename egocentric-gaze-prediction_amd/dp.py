@@ -407,3 +407,5 @@ def sync_buffers(module: torch.nn.Module):
                 b.copy_(h)
             else:
                 dist.broadcast(b, src=0)
+        from . import hipops
+        hipops.touch_params(list(module.buffers()))      # a collective need not move torch's version counter: declare the write

@@ -29,10 +29,12 @@ class GraphedModule:
         """Changes whenever a parameter was rewritten (torch version counter, the fused optimizer's per-parameter epoch, a
         wholesale overwrite) or re-allocated: the packed weights inside the captured graph would then be stale."""
         v = e = 0
+        ptrs = []       # every address: ``p.data = new`` moves neither counter, and it need not be the first parameter that moved
         for p in self._params:
             v += p._version
             e += getattr(p, "_egz_epoch", 0)
-        return (H._WEIGHT_EPOCH[0], v, e, self._params[0].data_ptr() if self._params else 0)
+            ptrs.append(p.data_ptr())
+        return (H._WEIGHT_EPOCH[0], v, e, ptrs)
 
     def _capture(self):
         side = torch.cuda.Stream()
@@ -70,7 +72,9 @@ class GraphedTrainStep:
     optimizer must be a FusedAdam (its step counter moves to the device).  Inside the capture every weight-gradient fork joins
     back (functions._close_fork), BatchNorm running statistics and ``num_batches_tracked`` are updated by kernels, so a replay
     is exactly one eager step.  The first ``warm`` calls run eagerly (real steps: lazy packings, workspaces and helper
-    streams come into being), the next one is captured.
+    streams come into being), the next one is captured.  A replay moves no host-side version or epoch: evaluate between two
+    replays of one step object only after ``H.touch_params`` on the model's parameters and buffers ("Writes
+    behind torch's back").
 
     For single-chain models (late_fusion, lstmnet, the stream pre-training VGG: streamtrain.GraphedStreamStep).  The two-stream
     SP step is NOT capturable this way -- its encoder streams and
@@ -112,18 +116,21 @@ class GraphedTrainStep:
                 self._unit()
             self.opt.step_count = count          # the capture ran the host side of step() without executing anything
             self.graph = g
-            self._versions = [p._version for p in self.opt.params]
+            self._tags = [H._tag(p) for p in self.opt.params]
             self._extra_sig = self._extra_signature()
             g.replay()
             self.opt.note_replays(1)
         else:
             # the captured step rebuilds the packed weights AFTER its Adam update (FusedAdam.step -> H.refresh_packings), so its
-            # forward pass trusts them: parameters overwritten from outside between two replays (load_state_dict, copy_)
-            # must be repacked here
-            versions = [p._version for p in self.opt.params]
-            if versions != self._versions:
-                H.refresh_packings(self.opt.params, force=True)
-                self._versions = versions
+            # forward pass trusts them: parameters overwritten from outside between two replays must be repacked here.  The
+            # full tag is compared: the version counter sees load_state_dict and copy_, the per-parameter and the global epoch
+            # see the writes torch cannot (``p.data.copy_`` + H.touch_params, H.bump_weight_epoch; a replay itself moves none
+            # of them -- the captured step's own touch_params ran on the host once, at capture time)
+            tags = [H._tag(p) for p in self.opt.params]
+            if tags != self._tags:
+                H.refresh_packings(self.opt.params, force=True)      # the fragment-ordered packings, one launch
+                H.repack_stale(self.opt.params)                      # ... and whatever else is cached (plane-ordered kinds)
+                self._tags = tags
             if self.extra:
                 sig = self._extra_signature()
                 if sig[1] != self._extra_sig[1]:
@@ -139,7 +146,10 @@ class GraphedTrainStep:
         return self.out
 
     def _extra_signature(self):
-        return ([(p._version, getattr(p, "_egz_epoch", 0)) for p in self.extra], [p.data_ptr() for p in self.extra])
+        """(what says the values changed, the addresses): the full tag of every extra parameter, the global epoch included --
+        a declared ``.data`` write (H.touch_params, H.bump_weight_epoch) repacks like a counted one."""
+        tags = [H._tag(p) for p in self.extra]
+        return ([t[:3] for t in tags], [t[3] for t in tags])
 
     def close(self):
         self.opt.set_capturable(False)

@@ -19,13 +19,18 @@ _USED = set()                     # packings requested by a launch since their l
 
 
 def bump_weight_epoch():
-    """Invalidate every packing (parameters were overwritten wholesale behind torch's back, e.g. a DP broadcast)."""
+    """Invalidate every packing (parameters were overwritten wholesale behind torch's back, e.g. a DP broadcast).
+    The blunt half of the rule for writes torch cannot see ("Writes behind torch's back"): every packed
+    weight, BatchNorm fold and eval row of every model is rebuilt at its next use, and a captured step repacks."""
     _WEIGHT_EPOCH[0] += 1
 
 
 def touch_params(params):
     """Called by the fused optimizer after it rewrote THESE parameters through its flat buffer (no torch version bump):
-    only their packings go stale -- a second optimizer (the AT module's) must not invalidate the SP model's."""
+    only their packings go stale -- a second optimizer (the AT module's) must not invalidate the SP model's.
+    Also what a caller owes after writing a parameter or a BatchNorm buffer through ``.data``, ``dist.broadcast(p.data)`` or a
+    raw pointer ("Writes behind torch's back"): such a write moves neither the version counter nor the
+    address, so nothing else can see it."""
     for p in params:
         p._egz_epoch = getattr(p, "_egz_epoch", 0) + 1
 

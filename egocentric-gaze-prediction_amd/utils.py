@@ -147,19 +147,23 @@ def make_layers(cfg, in_channels, batch_norm=True):
 def init_like_reference(root: nn.Module):
     """The init both model_SP and late_fusion apply to every sub-module (models/model_SP.py:52-65,
     models/late_fusion.py:25-38): Conv2d ~ N(0, sqrt(2/(kh*kw*Cout))) (fan-out), zero bias; BatchNorm
-    gamma 1 / beta 0; Linear ~ N(0, 0.01).  Conv3d is not matched and keeps torch's default init."""
-    for m in root.modules():
-        if isinstance(m, nn.Conv2d):
-            fan_out = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
-            m.weight.data.normal_(0, math.sqrt(2. / fan_out))
-            if m.bias is not None:
-                m.bias.data.zero_()
-        elif isinstance(m, nn.BatchNorm2d):
-            m.weight.data.fill_(1)
-            m.bias.data.zero_()
-        elif isinstance(m, nn.Linear):
-            m.weight.data.normal_(0, 0.01)
-            m.bias.data.zero_()
+    gamma 1 / beta 0; Linear ~ N(0, 0.01).  Conv3d is not matched and keeps torch's default init.
+    The reference writes through ``.data``; here the same in-place ops (the same random draws) run on the parameters themselves
+    under ``no_grad``, so that torch's version counters move: a module that has already run a forward has packed weights,
+    BatchNorm folds and eval rows cached under those counters (hipops.packing._tag), and a ``.data`` write is invisible to them."""
+    with torch.no_grad():
+        for m in root.modules():
+            if isinstance(m, nn.Conv2d):
+                fan_out = m.kernel_size[0] * m.kernel_size[1] * m.out_channels
+                m.weight.normal_(0, math.sqrt(2. / fan_out))
+                if m.bias is not None:
+                    m.bias.zero_()
+            elif isinstance(m, nn.BatchNorm2d):
+                m.weight.fill_(1)
+                m.bias.zero_()
+            elif isinstance(m, nn.Linear):
+                m.weight.normal_(0, 0.01)
+                m.bias.zero_()
 
 
 def owned_state_dict(module):
