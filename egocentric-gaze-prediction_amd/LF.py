@@ -1,6 +1,7 @@
 """Mirror of the reference's ``LF.py``: driver of the late-fusion module (LF.py:16-161) -- file listing with
 leave-one-subject-out split, Adam, train / validation loops with per-batch AAE / AUC, best-train and best-val
-checkpoints.  Model, loss and optimizer are the HIP-backed mirrors."""
+checkpoints.  Model, loss and optimizer are the HIP-backed mirrors.  ``LF(resident=True)`` keeps the three maps of every
+frame in device memory and gathers each batch there (data/late_resident.py); the default reads the files as the reference."""
 import os
 
 import torch
@@ -37,12 +38,14 @@ class GraphedLateIteration:
     RING = 16
 
     def __init__(self, model, criterion, optimizer, example):
+        """``example``: (feat, im, gt), or (fused, gt) of a resident batch (data.late_resident: the two maps come out of the
+        gather as the (B,2,H,W) tensor the fusion stack reads, so no cat2_planes launch is in the step)."""
         from .graphs import GraphedTrainStep
 
-        def fwd_loss(feat_, im_, gt_):
-            o = model(feat_, im_)                             # channel 0 = AT map, channel 1 = SP map (LF.py:90)
-            l = criterion(o, gt_)
-            rows, _ = aae_auc_rows(o, gt_)                    # device kernel, maps stay in HBM (LF.py:92-94)
+        def fwd_loss(*maps):
+            o = _forward(model, maps)
+            l = criterion(o, maps[-1])
+            rows, _ = aae_auc_rows(o, maps[-1])               # device kernel, maps stay in HBM (LF.py:92-94)
             return l, o, rows
         self.step = GraphedTrainStep(fwd_loss, optimizer, example)
         self.shape = tuple(example[0].shape)
@@ -50,8 +53,8 @@ class GraphedLateIteration:
         self.h_loss = torch.empty((self.RING,), dtype=torch.float32).pin_memory()
         self.pending = 0
 
-    def __call__(self, feat, im, gt):
-        loss, out, rows = self.step(feat, im, gt)
+    def __call__(self, *maps):
+        loss, out, rows = self.step(*maps)
         self.h_rows[self.pending].copy_(rows, non_blocking=True)
         self.h_loss[self.pending].copy_(loss, non_blocking=True)
         self.pending += 1
@@ -81,11 +84,36 @@ def _stage_late(sample, device):
     return tuple(sample[k].float().to(device, non_blocking=True) for k in ('im', 'gt', 'feat'))
 
 
+def _stage_late_resident(sample, device):
+    """(fused, gt) of a resident batch: one gather launch on the copy stream; staged_batches reads its status at hand-over."""
+    return sample['resident'].gather(sample, device)
+
+
+def _maps(staged):
+    """A staged batch in the step's argument order: (feat, im, gt) of the file loader, (fused, gt) of the resident set."""
+    if len(staged) == 2:
+        return staged
+    im, gt, feat = staged
+    return feat, im, gt
+
+
+def _forward(model, maps):
+    if len(maps) == 2:                                        # the gather built late_fusion.forward's Cat2Planes tensor
+        return model.fusion(maps[0], fuse_sigmoid=True)
+    return model(maps[0], maps[1])                            # channel 0 = AT map, channel 1 = SP map (LF.py:90)
+
+
 class LF():
+    stage = staticmethod(_stage_late)           # staged_batches' stage function; resident=True replaces it on the instance
+
     def __init__(self, pretrained_model=None, save_path='save', late_save_img='loss_late.png',
                  save_name='best_late.pth.tar', device='0', late_pred_path='../new_pred', num_epoch=10,
                  late_feat_path='../new_feat', gt_path='../gtea_gts', val_name='Alireza', batch_size=32,
-                 loss_function='f', lr=1e-7, task=None):
+                 loss_function='f', lr=1e-7, task=None, resident=False, decode='host', resident_gb=None):
+        """``resident``: both datasets are data.late_resident.ResidentLateDatasets, filled here (``decode``: how the one-time
+        fill decodes; ``resident_gb``: the device memory both pools may take, default 0.8 x what is free); the loaders, their
+        samplers and their RNG draws stay the file loader's, so a seeded run draws the same batches.  Under
+        torch.distributed every rank fills its own full pool."""
         self.model = late_fusion()
         self.device = torch.device('cuda:' + device)
         self.save_name, self.save_path = save_name, save_path
@@ -104,15 +132,26 @@ class LF():
         listTrainFeats, listValFeats = _split(late_feat_path, val_name, task)
         assert(len(listTrainFeats) == len(listTrainFiles) and len(listGtFiles) > 0)
         assert(len(listValGtFiles) == len(listValFiles))
-        train_set = lateDataset(late_pred_path, gt_path, late_feat_path, listTrainFiles, listGtFiles, listTrainFeats)
-        val_set = lateDataset(late_pred_path, gt_path, late_feat_path, listValFiles, listValGtFiles, listValFeats)
+        if resident:                           # the planes live on the device; batches are gathered there (data/late_resident.py)
+            from .data.late_resident import ResidentLateDataset
+            from .data.resident import fill_all
+            train_set = ResidentLateDataset(late_pred_path, gt_path, late_feat_path, listTrainFiles, listGtFiles,
+                                            listTrainFeats, decode=decode)
+            val_set = ResidentLateDataset(late_pred_path, gt_path, late_feat_path, listValFiles, listValGtFiles, listValFeats,
+                                          decode=decode)
+            fill_all((train_set, val_set), self.device, resident_gb, flag="--late_resident")
+            self.stage = _stage_late_resident
+        else:
+            train_set = lateDataset(late_pred_path, gt_path, late_feat_path, listTrainFiles, listGtFiles, listTrainFeats)
+            val_set = lateDataset(late_pred_path, gt_path, late_feat_path, listValFiles, listValGtFiles, listValFeats)
+        collate = getattr(train_set, 'collate_fn', None)
         # rank-sharded under torch.distributed (dp.RankShardSampler); the reference's loaders (LF.py:69-72) at world 1
         self.train_sampler = dp.RankShardSampler(train_set, True, batch_size) if dp.world_size() > 1 else None
         val_sampler = dp.RankShardSampler(val_set, False, batch_size, pad=False) if dp.world_size() > 1 else None
         self.train_loader = DataLoader(dataset=train_set, batch_size=batch_size, shuffle=self.train_sampler is None,
-                                       sampler=self.train_sampler, num_workers=0, pin_memory=True)
+                                       sampler=self.train_sampler, num_workers=0, pin_memory=True, collate_fn=collate)
         self.val_loader = DataLoader(dataset=val_set, batch_size=batch_size, shuffle=False, sampler=val_sampler,
-                                     num_workers=0, pin_memory=True)
+                                     num_workers=0, pin_memory=True, collate_fn=getattr(val_set, 'collate_fn', None))
         self.criterion = (floss() if loss_function == 'f' else BCELoss()).to(self.device)
         self.optimizer = FusedAdam(self.model.parameters(), lr=lr)
         self.reducer = dp.attach(self.optimizer) if torch.distributed.is_initialized() else None
@@ -146,11 +185,13 @@ class LF():
                 auc.update(auc1)
                 aae.update(aae1)
                 losses.update(loss1)
-        for i, (sample, (im, gt, feat)) in _progress(enumerate(staged_batches(loader, self.device, _stage_late))):
+        for i, (sample, staged) in _progress(enumerate(staged_batches(loader, self.device, self.stage))):
+            maps = _maps(staged)                              # (feat, im, gt), or (fused, gt) of a resident batch
+            gt = maps[-1]
             if use_graph and graphed is None:
-                graphed = self._graphed = GraphedLateIteration(self.model, self.criterion, self.optimizer, (feat, im, gt))
-            if graphed is not None and tuple(feat.shape) == graphed.shape:
-                graphed(feat, im, gt)                         # one replay = one LF.trainLate iteration (LF.py:90-100)
+                graphed = self._graphed = GraphedLateIteration(self.model, self.criterion, self.optimizer, maps)
+            if graphed is not None and tuple(maps[0].shape) == graphed.shape:
+                graphed(*maps)                                # one replay = one LF.trainLate iteration (LF.py:90-100)
                 if graphed.full or (i + 1) % every == 0:
                     _update(graphed.drain())
                 if (i + 1) % every == 0:
@@ -160,7 +201,7 @@ class LF():
                 continue
             if graphed is not None:
                 _update(graphed.drain())                      # (a trailing partial batch: the meters stay in iteration order)
-            out = self.model(feat, im)                       # channel 0 = AT map, channel 1 = SP map (LF.py:90)
+            out = _forward(self.model, maps)
             loss = self.criterion(out, gt)
             aae1, auc1, _ = computeAAEAUC(out.detach(), gt)          # device kernel, maps stay in HBM (LF.py:92-94)
             auc.update(auc1)

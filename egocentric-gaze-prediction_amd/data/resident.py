@@ -20,6 +20,109 @@ from .STdatas import STDataset, sniff
 COLS = 22                                   # table columns: image, 20 flow planes, ground truth
 
 
+# ----------------------------------------------------------------------------- the one-time fill, shared by the resident datasets
+# (this class and data.late_resident.ResidentLateDataset): a planned dataset has ``files`` [(path, first plane, channels)],
+# ``planes``, ``hw``, ``plane_table``, ``needed_bytes`` and ``decode``
+def _read(path):
+    try:
+        with open(path, 'rb') as f:
+            return f.read()
+    except OSError as e:
+        raise RuntimeError(f"{path}: unreadable: {e}") from e
+
+
+def _host_decode(path, channels):
+    try:
+        a = imread(path, gray=channels == 1)
+    except Exception as e:
+        raise RuntimeError(f"{path}: unreadable: {e}") from e
+    return a[None] if a.ndim == 2 else a.transpose((2, 0, 1))
+
+
+def _size_of(path, channels):
+    size = sniff(_read(path))
+    return tuple(size) if size is not None else tuple(_host_decode(path, channels).shape[1:])
+
+
+def fill_pool(files, hw, decode, device, chunk):
+    """Decodes ``files`` [(path, first plane, channels)], ``chunk`` files at a time, straight into their planes of a new uint8
+    (planes, h, w) pool on ``device``: decode='gpu' sends the files ``sniff`` takes through hipops.jpeg_decode, everything else
+    goes through _io.imread and a pinned staging buffer.  Corrupt data warns, naming the file; an unsupported, unreadable or
+    wrongly sized file raises, naming it.  -> the pool; the work may still be in flight on the current stream."""
+    from .. import hipops as H
+    h, w = hw
+    pool = torch.empty((files[-1][1] + files[-1][2], h, w), dtype=torch.uint8, device=device)
+    stage = torch.empty((min(chunk, len(files)) * max(f[2] for f in files), h, w), dtype=torch.uint8, pin_memory=True)
+    pending = []                            # (host status words, event, paths) of the decode launches in flight
+    for c0 in range(0, len(files), chunk):
+        streams, offs, planes, chans, paths, host_idx, n_host = [], [0], [], [], [], [], 0
+        if pending:                         # the staging buffer is reused: the chunk before has left it
+            pending[-1][1].synchronize()
+        for path, plane, channels in files[c0:c0 + chunk]:
+            data = _read(path) if decode == 'gpu' else None
+            size = sniff(data) if data is not None else None
+            if size is not None:
+                streams.append(data)
+                offs.append(offs[-1] + len(data))
+                planes.append(plane)
+                chans.append(channels)
+                paths.append(path)
+            else:
+                a = _host_decode(path, channels)
+                size = a.shape[1:]
+                if tuple(size) == (h, w):
+                    stage[n_host:n_host + channels].copy_(torch.from_numpy(np.array(a)))
+                    host_idx.extend(range(plane, plane + channels))
+                    n_host += channels
+            if tuple(size) != (h, w):
+                raise RuntimeError(f"{path}: {tuple(size)} pixels, the dataset's first file has {(h, w)}")
+        host = None
+        if streams:
+            blob = torch.frombuffer(bytearray(b"".join(streams)), dtype=torch.uint8).to(device)
+            _, status = H.jpeg_decode(blob, offs, (h, w), chans, out=pool, planes=planes, n3=sum(c == 3 for c in chans))
+            host = torch.empty(len(streams), dtype=torch.int32, pin_memory=True)
+            host.copy_(status, non_blocking=True)
+        if n_host:
+            pool.index_copy_(0, torch.tensor(host_idx, dtype=torch.int64).to(device, non_blocking=True),
+                             stage[:n_host].to(device, non_blocking=True))
+        ev = torch.cuda.Event()
+        ev.record()
+        pending.append((host, ev, paths))
+    for host, ev, paths in pending:         # check_decode_status's rules
+        ev.synchronize()
+        if host is None:
+            continue
+        for i in torch.nonzero(host).flatten().tolist():
+            st = int(host[i])
+            if st == 1:
+                warnings.warn(f"{paths[i]}: {H.JPEG_STATUS[1]} (decoded with zero padding, as libjpeg does)", RuntimeWarning)
+            else:
+                raise RuntimeError(f"{paths[i]}: GPU JPEG decode failed: {H.JPEG_STATUS.get(st, st)}")
+    return pool
+
+
+def fill_planned(ds, device, budget_bytes, chunk, who, flag):
+    """``fill`` of a planned resident dataset ``ds``: refuses before allocating when ``needed_bytes`` exceeds ``budget_bytes``
+    (None: 0.8 x the free device memory; ``who`` / ``flag`` name the caller and its CLI switch in the message), fills the pool
+    (fill_pool), puts the table beside it and prints the number of files, the bytes and the seconds once."""
+    device = torch.device(device)
+    if budget_bytes is None:
+        budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
+    if ds.needed_bytes > budget_bytes:
+        raise RuntimeError(f"{who}: the decoded dataset needs {ds.needed_bytes} bytes "
+                           f"({ds.planes} planes of {ds.hw[0]} x {ds.hw[1]}), {budget_bytes} bytes are allowed: "
+                           f"run without {flag} (there is no partial cache)")
+    t0 = time.perf_counter()
+    pool = fill_pool(ds.files, ds.hw, ds.decode, device, chunk)
+    ds.table = ds.plane_table.to(device)
+    torch.cuda.synchronize(device)          # the gathers run on other streams (staged_batches' copy stream)
+    ds.pool = pool
+    ds.fill_seconds = time.perf_counter() - t0
+    print(f"resident dataset: {len(ds.files)} files decoded ({ds.decode}) into {ds.planes} planes, "
+          f"{ds.needed_bytes} bytes on {device}, {ds.fill_seconds:.2f} s")
+    return ds
+
+
 class ResidentSTDataset(STDataset):
     """``STDataset`` whose planes live on the device.  ``decode`` selects how ``fill`` decodes ('gpu': hipops.jpeg_decode
     for the files ``sniff`` takes, the host for the rest); ``gpu_fields`` is honoured as in ``STDataset``: files of a field
@@ -70,25 +173,10 @@ class ResidentSTDataset(STDataset):
         self._plan = fields
         return self
 
-    @staticmethod
-    def _read(path):
-        try:
-            with open(path, 'rb') as f:
-                return f.read()
-        except OSError as e:
-            raise RuntimeError(f"{path}: unreadable: {e}") from e
+    _read, _host_decode = staticmethod(_read), staticmethod(_host_decode)
 
     def _size_of(self, path, channels):
-        size = sniff(self._read(path))
-        return tuple(size) if size is not None else tuple(self._host_decode(path, channels).shape[1:])
-
-    @staticmethod
-    def _host_decode(path, channels):
-        try:
-            a = imread(path, gray=channels == 1)
-        except Exception as e:
-            raise RuntimeError(f"{path}: unreadable: {e}") from e
-        return a[None] if a.ndim == 2 else a.transpose((2, 0, 1))
+        return _size_of(path, channels)
 
     # ------------------------------------------------------------------ fill (decode once)
     def fill(self, device, budget_bytes=None, chunk=704):
@@ -98,70 +186,7 @@ class ResidentSTDataset(STDataset):
         raises, naming it.  Prints the number of files, the bytes and the seconds once."""
         if self._plan != tuple(self.gpu_fields):
             self.plan()
-        device = torch.device(device)
-        if budget_bytes is None:
-            budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
-        if self.needed_bytes > budget_bytes:
-            raise RuntimeError(f"ResidentSTDataset.fill: the decoded dataset needs {self.needed_bytes} bytes "
-                               f"({self.planes} planes of {self.hw[0]} x {self.hw[1]}), {budget_bytes} bytes are allowed: "
-                               "run without --gpu_resident (there is no partial cache)")
-        from .. import hipops as H
-        t0 = time.perf_counter()
-        h, w = self.hw
-        pool = torch.empty((self.planes, h, w), dtype=torch.uint8, device=device)
-        stage = torch.empty((min(chunk, len(self.files)) * 3, h, w), dtype=torch.uint8, pin_memory=True)
-        pending = []                        # (host status words, event, paths) of the decode launches in flight
-        for c0 in range(0, len(self.files), chunk):
-            streams, offs, planes, chans, paths, host_idx, n_host = [], [0], [], [], [], [], 0
-            if pending:                     # the staging buffer is reused: the chunk before has left it
-                pending[-1][1].synchronize()
-            for path, plane, channels in self.files[c0:c0 + chunk]:
-                data = self._read(path) if self.decode == 'gpu' else None
-                size = sniff(data) if data is not None else None
-                if size is not None:
-                    streams.append(data)
-                    offs.append(offs[-1] + len(data))
-                    planes.append(plane)
-                    chans.append(channels)
-                    paths.append(path)
-                else:
-                    a = self._host_decode(path, channels)
-                    size = a.shape[1:]
-                    if tuple(size) == (h, w):
-                        stage[n_host:n_host + channels].copy_(torch.from_numpy(np.array(a)))
-                        host_idx.extend(range(plane, plane + channels))
-                        n_host += channels
-                if tuple(size) != (h, w):
-                    raise RuntimeError(f"{path}: {tuple(size)} pixels, the dataset's first file has {(h, w)}")
-            host = None
-            if streams:
-                blob = torch.frombuffer(bytearray(b"".join(streams)), dtype=torch.uint8).to(device)
-                _, status = H.jpeg_decode(blob, offs, (h, w), chans, out=pool, planes=planes, n3=sum(c == 3 for c in chans))
-                host = torch.empty(len(streams), dtype=torch.int32, pin_memory=True)
-                host.copy_(status, non_blocking=True)
-            if n_host:
-                pool.index_copy_(0, torch.tensor(host_idx, dtype=torch.int64).to(device, non_blocking=True),
-                                 stage[:n_host].to(device, non_blocking=True))
-            ev = torch.cuda.Event()
-            ev.record()
-            pending.append((host, ev, paths))
-        for host, ev, paths in pending:     # check_decode_status's rules
-            ev.synchronize()
-            if host is None:
-                continue
-            for i in torch.nonzero(host).flatten().tolist():
-                st = int(host[i])
-                if st == 1:
-                    warnings.warn(f"{paths[i]}: {H.JPEG_STATUS[1]} (decoded with zero padding, as libjpeg does)", RuntimeWarning)
-                else:
-                    raise RuntimeError(f"{paths[i]}: GPU JPEG decode failed: {H.JPEG_STATUS.get(st, st)}")
-        self.table = self.plane_table.to(device)
-        torch.cuda.synchronize(device)      # the gathers run on other streams (staged_batches' copy stream)
-        self.pool = pool
-        self.fill_seconds = time.perf_counter() - t0
-        print(f"resident dataset: {len(self.files)} files decoded ({self.decode}) into {self.planes} planes, "
-              f"{self.needed_bytes} bytes on {device}, {self.fill_seconds:.2f} s")
-        return self
+        return fill_planned(self, device, budget_bytes, chunk, "ResidentSTDataset.fill", "--gpu_resident")
 
     # ------------------------------------------------------------------ samples
     def __getitem__(self, index):
@@ -187,18 +212,18 @@ class ResidentSTDataset(STDataset):
         return H.resident_gather(self.pool, self.table, idx, fields=fields, raw=raw, prepare=prepare, status_to=sample)
 
 
-def fill_all(datasets, device, budget_gb=None):
-    """Fills several resident datasets (the training and the validation set of a script) under ONE budget: ``budget_gb``
-    GB, or 0.8 x the free memory of ``device``.  All are planned first, so a set that does not fit raises before any pool is
-    allocated."""
+def fill_all(datasets, device, budget_gb=None, flag="--gpu_resident"):
+    """Fills several resident datasets (the training and the validation set of a script; ResidentSTDatasets,
+    ResidentLateDatasets or a mix) under ONE budget: ``budget_gb`` GB, or 0.8 x the free memory of ``device``.  All are planned
+    first, so a set that does not fit raises before any pool is allocated.  ``flag``: the CLI switch the refusal names."""
     datasets = [ds for ds in datasets if len(ds)]
     for ds in datasets:
         ds.plan()
     budget = int(budget_gb * 1e9) if budget_gb is not None else int(0.8 * torch.cuda.mem_get_info(torch.device(device))[0])
     needed = sum(ds.needed_bytes for ds in datasets)
     if needed > budget:
-        raise RuntimeError(f"--gpu_resident: the decoded datasets need {needed} bytes, {budget} bytes are allowed: "
-                           "run without --gpu_resident (there is no partial cache)")
+        raise RuntimeError(f"{flag}: the decoded datasets need {needed} bytes, {budget} bytes are allowed: "
+                           f"run without {flag} (there is no partial cache)")
     for ds in datasets:
         ds.fill(device, budget_bytes=budget)
         budget -= ds.needed_bytes

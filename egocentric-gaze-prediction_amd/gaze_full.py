@@ -58,6 +58,9 @@ def build_parser():
     a('--gpu_resident_gb', type=float, default=argparse.SUPPRESS,
       help='device memory the resident dataset may take, in GB, shared by the training and validation sets '
            '(default: 0.8 x what is free)')
+    a('--late_resident', action='store_true', default=argparse.SUPPRESS,
+      help="LF stage: decode the extracted SP / AT maps and the ground truth once and keep the planes in device memory "
+           "(data.late_resident); batches are gathered on the GPU.  Honours --gpu_decode and --gpu_resident_gb")
     return p
 
 
@@ -184,11 +187,25 @@ def main(argv=None):
         _at_stage(args, STTrainData, STValData)
     else:
         _at_stage_sharded(args, STTrainData, STValData)
+    _lf_stage(args, (STTrainData, STValData))
+
+
+def _lf_stage(args, st_data=()):
+    """The LF stage.  ``--late_resident``: its two datasets are decoded once into device memory (data/late_resident.py), on the
+    GPU with ``--gpu_decode``, within ``--gpu_resident_gb``; the pools of ``--gpu_resident`` (``st_data``) are released first."""
+    from .LF import LF
+    late_resident = getattr(args, 'late_resident', False)
+    decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
+    if late_resident:                       # nothing after the AT stage reads the ST pools: their memory goes to the LF pools
+        for data in st_data:
+            if getattr(data, 'pool', None) is not None:
+                data.pool = data.table = None
+        torch.cuda.empty_cache()
     lf = LF(pretrained_model=args.pretrained_late, save_path=args.save_path, late_save_img=args.late_save_img,
             save_name=args.save_late, device=args.device, late_pred_path=args.extract_late_pred_folder,
             num_epoch=args.num_epoch, late_feat_path=args.extract_late_feat_folder, gt_path=args.gtPath,
             val_name=args.val_name, batch_size=args.batch_size, loss_function=args.loss_function, lr=args.lr_late,
-            task=args.task)
+            task=args.task, resident=late_resident, decode=decode, resident_gb=getattr(args, 'gpu_resident_gb', None))
     if args.train_late:
         lf.train()
     else:

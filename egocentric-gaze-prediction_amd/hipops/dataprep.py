@@ -1,4 +1,4 @@
-"""Dataset preparation and input pipeline: gaze maps, u8 normalise, the resident gather, AT glue."""
+"""Dataset preparation and input pipeline: gaze maps, u8 normalise, the resident gathers (SP / AT and late fusion), AT glue."""
 from __future__ import annotations
 
 import sys
@@ -203,6 +203,46 @@ def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, 
     else:
         _H.check_resident_status((host, done))
     return out_raw if raw else (image, flow, gt)
+
+
+def late_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, raw: bool = False,
+                status_to: Optional[dict] = None):
+    """A late-fusion batch gathered from a pool of decoded planes on the device (egz_late_gather).
+
+    pool: uint8 (P, H, W); table: int64 (N, 3) plane numbers (SP prediction, AT map, ground truth); idx: int64 (B,) sample
+    numbers; all on the GPU.  -> ``(fused, gt)`` fp32 (B,2,H,W) / (B,1,H,W), every value u8 / 255 as data.lateDataset makes it
+    (bit-identical); fused channel 0 is the AT map and channel 1 the SP prediction, the tensor late_fusion's Cat2Planes would
+    build.  With ``raw=True`` instead the uint8 (B,3,H,W) bytes in table order.  The status word is handled as in
+    resident_gather."""
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
+            and pool.is_contiguous()):
+        raise ValueError("late_gather: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
+    dev = pool.device
+    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3
+            and table.is_contiguous()):
+        raise ValueError("late_gather: table must be a contiguous int64 (N, 3) tensor on the pool's device")
+    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
+        raise ValueError("late_gather: idx must be a contiguous int64 (B,) tensor on the pool's device")
+    P, H, W = pool.shape
+    B = idx.numel()
+    fused = gt = out_raw = None
+    if raw:
+        out_raw = torch.empty((B, 3, H, W), dtype=torch.uint8, device=dev)
+    else:
+        fused = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+        gt = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_late_gather(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W, _p(fused),
+                              _p(gt), _p(out_raw), status.data_ptr(), _stream()), "egz_late_gather")
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_resident_status'] = (host, done)
+    else:
+        _H.check_resident_status((host, done))
+    return out_raw if raw else (fused, gt)
 
 
 def crop_mean(feat_nhwc: torch.Tensor, gp, size: int, cell: int = 16) -> torch.Tensor:

@@ -466,6 +466,16 @@ int egz_u8_normalize(const unsigned char* src, float* dst, long n, long plane, i
 int egz_resident_gather(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H, int W,
                         const float* mean, const float* std, float* image, float* flow, float* gt, float* flow_nhwc32,
                         unsigned int* absmax, unsigned char* raw, int raw_fields, int* status, hipStream_t stream);
+/* A late-fusion batch gathered from such a pool (data/late_resident.py, csrc/batch_gather.hip).  pool (P, H, W) uint8; table
+ * (N, 3) int64 plane numbers per sample -- column 0 the SP prediction, 1 the AT map, 2 the ground truth; idx (B,) int64 sample
+ * numbers.  Outputs, each optional (null: not produced, nothing written): fused (B,2,H,W) fp32, channel 0 the AT map and
+ * channel 1 the SP prediction (the tensor egz_cat2_planes builds for models/late_fusion.py); gt (B,1,H,W) fp32; raw (B,3,H,W)
+ * uint8, the gathered bytes in table order.  Every fp32 value is (float)u8 / 255.f, the correctly rounded division:
+ * bit-identical with egz_u8_normalize(mean 0, std 1) of the gathered bytes.  H * W % 4 == 0; pool offsets are 64-bit.  A sample
+ * number, or a table entry of an output asked for, that is out of range is not dereferenced: that sample is skipped and
+ * *status (device, zero-filled by the caller) gets bit 0 (idx) or bit 1 (table). */
+int egz_late_gather(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H, int W,
+                    float* fused, float* gt, unsigned char* raw, int* status, hipStream_t stream);
 /* AT extraction glue (AT.py:25-39,58-66,229; extractLSTMw.py:81-90): chn_weight = mean of the size x size window of the
  * channels-last (B,H,W,C) feature map around gaze_point / cell; weighted map = min-max normalised sum_c feat * w. */
 int egz_crop_mean(const float* feat, const int* gp, float* out, int B, int H, int W, int C, int size, int cell,
