@@ -134,6 +134,16 @@ def get_weighted(chn_weight, feature):
 AT_GRAPH = os.environ.get("EGAZE_AT_GRAPH", "1") != "0"      # A/B knob: 0 = issue every sample step launch by launch
 
 
+def _carry_state(state, hn, cn):
+    """state (2, L, 1, C) = (hn, cn) of a step.  They share one buffer on the single-step path: one copy carries both."""
+    base = getattr(hn, "_base", None)
+    if base is not None and base is getattr(cn, "_base", None) and base.numel() == state.numel() and base.is_contiguous():
+        H.copy_into(state, base.detach())
+    else:
+        H.copy_into(state[0], hn.detach().contiguous())
+        H.copy_into(state[1], cn.detach().contiguous())
+
+
 class _GraphedSampleStep:
     """One training step of AT.trainLSTM's loop captured into a hipGraph (the reference issues it per fixation sample,
     AT.py:127-145; ~20 launches plus autograd and optimizer bookkeeping on the host every time):
@@ -144,11 +154,16 @@ class _GraphedSampleStep:
     so the forward pass of sample i-1 is deferred until target i is known -- the parameters it sees are the same (those
     after the update of iteration i-1) and so is every loss, every update and the carried state.  Inputs, state and loss live
     in static buffers; the Adam step counter lives on the device (FusedAdam.set_capturable).  The first ``WARM`` steps run
-    eagerly through the same function (they are real training steps), then the step is captured once and replayed."""
+    eagerly through the same function (they are real training steps), then the step is captured once and replayed.
+
+    ``fetch = (pool, plan, cursor, status)`` (a filled data.lstm_resident.ResidentLSTMDataset): the step's first launch is
+    hipops.lstm_pool_fetch, which writes ``both`` and resets ``state`` off the device-side cursor -- in place of step()'s
+    host copy and the caller's reset_state(); every launch after it is the same."""
     WARM = 3
 
-    def __init__(self, lstm, criterion, optimizer, device, width, ring=None):
+    def __init__(self, lstm, criterion, optimizer, device, width, ring=None, fetch=None):
         self.lstm, self.criterion, self.opt = lstm, criterion, optimizer
+        self.fetch = fetch
         # ``ring``: device float tensor in which the loss of every step is parked, slot = (optimizer steps completed before the
         # step) % len(ring) -- written by the loss kernel itself off the optimizer's device-side step counter, so reading the
         # losses back once per ring costs no launch per replay
@@ -164,6 +179,9 @@ class _GraphedSampleStep:
         self.opt.set_capturable(True)
 
     def _unit(self):
+        if self.fetch is not None:
+            pool, plan, cursor, status = self.fetch
+            H.lstm_pool_fetch(pool, plan, cursor, self.both[0], self.both[1], self.state, status)
         pred, (hn, cn) = self.lstm(self.both[0], (self.state[0], self.state[1]))
         # criterion(pred, tanh(target)) AND its gradient for the unit seed of loss.backward() in one kernel (AT.py:138-141), which
         # also parks the loss in the ring: the backward pass starts at the network's output
@@ -173,22 +191,19 @@ class _GraphedSampleStep:
         self.opt.zero_grad(all_overwritten=self.single_step)
         pred.backward(gradient=dpred.view_as(pred))
         self.opt.step()
-        # (hn, cn) share one buffer on the single-step path: one copy carries the state over -- after the backward pass,
-        # which reads the incoming state
-        base = getattr(hn, "_base", None)
-        if base is not None and base is getattr(cn, "_base", None) and base.numel() == self.state.numel() and base.is_contiguous():
-            H.copy_into(self.state, base.detach())
-        else:
-            H.copy_into(self.state[0], hn.detach().contiguous())
-            H.copy_into(self.state[1], cn.detach().contiguous())
+        _carry_state(self.state, hn, cn)       # after the backward pass, which reads the incoming state
         self.loss = loss
 
     def reset_state(self):
         H.fill_zero(self.state)
 
-    def step(self, host_pair):
-        """host_pair: pinned (2, width) tensor = (input of the deferred sample, target of the current one) -> loss (0-d)."""
-        self.both.copy_(host_pair.view_as(self.both), non_blocking=True)
+    def step(self, host_pair=None):
+        """host_pair: pinned (2, width) tensor = (input of the deferred sample, target of the current one) -> loss (0-d);
+        None with ``fetch``: the step takes both from the pool."""
+        if (host_pair is None) != (self.fetch is not None):
+            raise RuntimeError("_GraphedSampleStep.step: a host pair or a resident fetch feeds the step, one of the two")
+        if host_pair is not None:
+            self.both.copy_(host_pair.view_as(self.both), non_blocking=True)
         self.calls += 1
         if self.graph is None and self.calls <= self.WARM:
             self._unit()
@@ -211,13 +226,52 @@ class _GraphedSampleStep:
         self.opt.set_capturable(False)
 
 
+class _GraphedEvalStep:
+    """One step of AT.testLSTM's loop over a filled ResidentLSTMDataset as a hipGraph of its own, captured under
+    torch.no_grad():  fetch -> lstm(inp, state) -> MSE(pred, tanh(target)) parked in ``losses[step]`` -> state carry.
+    The loss kernel is the training step's (hipops.mse_fwd_grad; its gradient output is discarded, its loss is bit-identical
+    with hipops.mse_fwd's, csrc/head_loss.hip) because it can park the loss itself: the slot is the step number the fetch
+    left in cursor[1].  Nothing is read back per step; no optimizer is involved."""
+    WARM = _GraphedSampleStep.WARM
+
+    def __init__(self, lstm, device, width, fetch, losses):
+        self.lstm, self.fetch, self.losses = lstm, fetch, losses
+        self.both = torch.zeros((2, 1, 1, width), device=device)
+        self.state = torch.zeros((2, lstm.num_layer, 1, lstm.num_channel), device=device)
+        self.graph, self.calls = None, 0
+
+    def _unit(self):
+        pool, plan, cursor, status = self.fetch
+        H.lstm_pool_fetch(pool, plan, cursor, self.both[0], self.both[1], self.state, status)
+        pred, (hn, cn) = self.lstm(self.both[0], (self.state[0], self.state[1]))
+        H.mse_fwd_grad(H._req(pred.detach().contiguous(), "pred"), self.both[1].view_as(pred).contiguous(), True,
+                       self.losses, cursor[1:])
+        _carry_state(self.state, hn, cn)
+
+    def step(self):
+        self.calls += 1
+        if self.graph is None and self.calls <= self.WARM:
+            self._unit()
+            return
+        if self.graph is None:
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with H.capture(g, eager_arena=False):
+                self._unit()
+            self.graph = g
+        self.graph.replay()
+
+
 class AT():
     def __init__(self, pretrained_model=None, pretrained_lstm=None, extract_lstm=False, crop_size=3,
                  num_epoch_lstm=30, lstm_save_img='loss_lstm.png', save_path='save', save_name='best_lstm.pth.tar',
                  device='0', lstm_data_path='../512w', traindata=None, valdata=None, task=None, align=False,
-                 shard=None):
+                 shard=None, resident=False, resident_gb=None):
         """``shard=(rank, world)``: with ``extract_lstm`` every rank of the default process group extracts its share of the
-        LSTM training data (extractLSTMw.extractw), then all meet at a barrier so that each lists the complete folders."""
+        LSTM training data (extractLSTMw.extractw), then all meet at a barrier so that each lists the complete folders.
+        ``resident``: both LSTM datasets are data.lstm_resident.ResidentLSTMDatasets, filled here on the device (``resident_gb``:
+        the device memory both pools may take, default 0.8 x what is free); trainLSTM / testLSTM then fetch every step on the
+        GPU (_epoch_resident) and compute what they compute from the files, bit for bit."""
         if pretrained_model is None:
             raise generalException('AT module have to use pretrained SP module.')
         self.device = torch.device('cuda:' + device)
@@ -243,10 +297,23 @@ class AT():
         self.model.to(self.device)
         self.model._modules.get(hook_name).register_forward_hook(hook_feature)
         from .data.LSTMdatas import lstmDataset
+        if resident:                           # the vectors live on the device; every step fetches there (data/lstm_resident.py)
+            from .data.lstm_resident import ResidentLSTMDataset as lstmDataset
         self.lstmTrainLoader = DataLoader(dataset=lstmDataset(os.path.join(lstm_data_path, 'train'), task),
                                           batch_size=1, shuffle=False, num_workers=0)
         self.lstmValLoader = DataLoader(dataset=lstmDataset(os.path.join(lstm_data_path, 'test'), task),
                                         batch_size=1, shuffle=False, num_workers=0)
+        if resident:                           # (after extract_lstm and its barrier: the folders are complete)
+            for loader in (self.lstmTrainLoader, self.lstmValLoader):
+                loader.dataset.fill(self.device, resident_gb)
+                if resident_gb is not None:    # one budget for both pools
+                    resident_gb -= loader.dataset.needed_bytes / 1e9
+
+    def release_resident(self):
+        """Frees the pools of ``resident=True``; the loaders go on reading the files."""
+        for loader in (self.lstmTrainLoader, self.lstmValLoader):
+            if hasattr(loader.dataset, 'release'):
+                loader.dataset.release()
 
     def reload_LSTM(self, pretrained_lstm):
         merged = self.lstm.state_dict()
@@ -314,7 +381,74 @@ class AT():
                 runner.close()
         return losses.avg
 
+    def _epoch_resident(self, dataset, train):
+        """trainLSTM's / testLSTM's loop over a filled ResidentLSTMDataset: the plan of the epoch (which vector is the input,
+        which the target, where the state is reset) is on the device beside the vectors, the step's graph begins with the
+        fetch that reads it off a device-side cursor, and the host issues one replay per sample and nothing else."""
+        losses = AverageMeter()
+        n = dataset.n_steps
+        if n == 0:                              # fewer than three files: no scored sample, as over the files
+            return losses.avg
+        width = dataset.pool.shape[1]
+        # {next step, step being run} and the fetch's sticky status word side by side, then (eval) one loss slot per step as
+        # float bits: ONE read-back covers all of them
+        buf = torch.zeros(3 + (0 if train else n), dtype=torch.int32, device=self.device)
+        fetch = (dataset.pool, dataset.plan, buf[:2], buf[2:3])
+
+        def check_ctl(words, done):
+            H.check_lstm_pool_status(words[2])
+            if words[0] != done:
+                raise RuntimeError(f"AT resident plan out of step: device cursor {words[0]}, host expected {done}")
+
+        if not train:
+            runner = _GraphedEvalStep(self.lstm, self.device, width, fetch, buf[3:].view(torch.float32))
+            with torch.no_grad():
+                for _ in range(n):
+                    runner.step()
+            host = buf.cpu()                    # the one synchronising read-back of the epoch
+            check_ctl(host[:3].tolist(), n)
+            for v in host[3:].view(torch.float32).tolist():
+                losses.update(v)
+            return losses.avg
+
+        RING = 64                               # as _epoch_graphed: the losses are read back once per RING // 2 samples
+        ring = torch.zeros(RING // 2, device=self.device)
+        runner = _GraphedSampleStep(self.lstm, self.criterion_lstm, self.optimizer_lstm, self.device, width, ring=ring,
+                                    fetch=fetch)
+        first, pending = self.optimizer_lstm.step_count, 0
+        start = first
+
+        def drain():
+            nonlocal pending, first
+            if pending:
+                vals = ring.cpu().tolist()
+                done = int(self.optimizer_lstm.step_dev[0].item())
+                if done != first + pending:
+                    raise RuntimeError(f"AT loss ring out of step: device counter {done}, host expected {first + pending}")
+                check_ctl(buf.tolist(), first + pending - start)
+                H.lstm_persist_check()
+                self.optimizer_lstm.check_finite()
+                for i in range(pending):
+                    losses.update(vals[(first + i) % len(vals)])
+                first += pending
+                pending = 0
+        try:
+            for _ in range(n):
+                runner.step()
+                pending += 1
+                if pending == RING // 2:
+                    drain()
+            drain()
+        finally:
+            runner.close()
+        return losses.avg
+
     def _epoch(self, loader, train):
+        dataset = getattr(loader, 'dataset', None)
+        if getattr(dataset, 'filled', False) and self.device.type == 'cuda':
+            from .models import LSTMnet as _L
+            if _L.B1_FUSED:
+                return self._epoch_resident(dataset, train)
         if train and AT_GRAPH and self.device.type == 'cuda':
             return self._epoch_graphed(loader)
         losses = AverageMeter()
@@ -369,6 +503,7 @@ class AT():
                 prev = l
                 torch.save(owned_state_dict(self.lstm), os.path.join(self.save_path, 'val' + self.save_name))
             plot_loss(loss_train, loss_val, os.path.join(self.save_path, self.lstm_save_img))
+        self.release_resident()                # nothing after the training reads the pools of ``resident=True``
         print('lstm training finished!')
 
     def extract_late(self, st_loader, pred_folder='../new_pred/', feat_folder='../new_feat/', chunk=32, shard=None):

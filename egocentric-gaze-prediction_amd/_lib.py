@@ -125,6 +125,7 @@ SIGNATURES = {
     "egz_u8_normalize": (c_int, [P, P, c_long, c_long, c_int, P, P, S]),
     "egz_resident_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P, S]),
     "egz_late_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, S]),
+    "egz_lstm_pool_fetch": (c_int, [P, c_long, c_int, P, P, P, c_long, P, P, P, P, c_long, P, S]),
     "egz_crop_mean": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, S]),
     "egz_window_mean": (c_int, [P, P, P, c_int, c_int, c_int, c_int, S]),
     "egz_pixel_weighted_sum": (c_int, [P, P, P, c_int, c_int, c_int, S]),

@@ -61,6 +61,9 @@ def build_parser():
     a('--late_resident', action='store_true', default=argparse.SUPPRESS,
       help="LF stage: decode the extracted SP / AT maps and the ground truth once and keep the planes in device memory "
            "(data.late_resident); batches are gathered on the GPU.  Honours --gpu_decode and --gpu_resident_gb")
+    a('--lstm_resident', action='store_true', default=argparse.SUPPRESS,
+      help="AT stage: read the extracted LSTM vectors once and keep them in device memory (data.lstm_resident); every step of "
+           "the LSTM training and validation fetches its input and target on the GPU.  Honours --gpu_resident_gb")
     return p
 
 
@@ -75,7 +78,8 @@ def _at_stage(args, STTrainData, STValData):
              extract_lstm=args.extract_lstm, crop_size=args.crop_size, num_epoch_lstm=args.num_epoch_lstm,
              lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
              device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
-             task=args.task, align=args.align)
+             task=args.task, align=args.align, resident=getattr(args, 'lstm_resident', False) and args.train_lstm,
+             resident_gb=getattr(args, 'gpu_resident_gb', None))
     if args.train_lstm:
         att.train()
     if args.extract_late:
@@ -100,7 +104,9 @@ def _at_stage_sharded(args, STTrainData, STValData):
              extract_lstm=args.extract_lstm, crop_size=args.crop_size, num_epoch_lstm=args.num_epoch_lstm,
              lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
              device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
-             task=args.task, align=args.align, shard=shard)
+             task=args.task, align=args.align, shard=shard,
+             resident=getattr(args, 'lstm_resident', False) and args.train_lstm and dp.is_main(),     # where AT.train runs
+             resident_gb=getattr(args, 'gpu_resident_gb', None))
     if args.train_lstm:
         if dp.is_main():
             try:

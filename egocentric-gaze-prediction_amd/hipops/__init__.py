@@ -126,10 +126,10 @@ from .loss import (  # noqa: E402,F401
     floss_fwd, mse_bwd, mse_fwd, mse_fwd_grad,
 )
 from .lstm import (  # noqa: E402,F401
-    _PERSIST_SYNC, _lstm_b1_dims, _persist_sync, add, copy_into, gemm, linear_fwd, lstm_b1_bwd, lstm_b1_fwd,
-    lstm_cell_bwd, lstm_cell_fwd, lstm_persist_bwd, lstm_persist_check, lstm_persist_errors, lstm_persist_fwd,
-    lstm_persist_ok, lstm_persist_status, lstm_persistent, lstm_wave_bwd, lstm_wave_fwd, matmul_nn, matmul_tn,
-    matmul_tn_batched, tanh_bwd, tanh_fwd, transpose2d,
+    LSTM_POOL_STATUS, _PERSIST_SYNC, _lstm_b1_dims, _persist_sync, add, check_lstm_pool_status, copy_into, gemm,
+    linear_fwd, lstm_b1_bwd, lstm_b1_fwd, lstm_cell_bwd, lstm_cell_fwd, lstm_persist_bwd, lstm_persist_check,
+    lstm_persist_errors, lstm_persist_fwd, lstm_persist_ok, lstm_persist_status, lstm_persistent, lstm_pool_fetch,
+    lstm_wave_bwd, lstm_wave_fwd, matmul_nn, matmul_tn, matmul_tn_batched, tanh_bwd, tanh_fwd, transpose2d,
 )
 from .metrics import _GAUSS_W, _gauss_weights, aae_auc  # noqa: E402,F401
 from .dataprep import (  # noqa: E402,F401

@@ -337,6 +337,60 @@ def lstm_b1_bwd(params, grads, dout, dhn, dcn, xt, acts, h0, c0, hn, cn, out):
                               C, Hd, N, ws.data_ptr(), nbytes, _stream()), "egz_lstm_b1_bwd")
 
 
+# ----------------------------------------------------------------------------- resident LSTM vectors (data/lstm_resident.py, --lstm_resident)
+LSTM_POOL_STATUS = {1: "the step cursor outside the plan", 2: "a plan row outside the pool",
+                    3: "the step cursor outside the plan and a plan row outside the pool"}
+
+
+def check_lstm_pool_status(word) -> None:
+    """Raises if the sticky status word of lstm_pool_fetch (already read back: an int) is not 0."""
+    st = int(word)
+    if st:
+        raise RuntimeError(f"lstm_pool_fetch: {LSTM_POOL_STATUS.get(st, st)}: the step was refused, nothing was fetched and the "
+                           f"cursor did not advance")
+
+
+def lstm_pool_fetch(pool: torch.Tensor, plan, cursor: torch.Tensor, inp: torch.Tensor, tgt: torch.Tensor,
+                    state: Optional[torch.Tensor], status: torch.Tensor) -> None:
+    """One step of the AT LSTM loops fetched on the device (egz_lstm_pool_fetch): with k = cursor[0], ``inp`` = pool[in_row[k]],
+    ``tgt`` = pool[tgt_row[k]], ``state`` (optional) zeroed if reset[k], then cursor = (k + 1, k).
+
+    pool: fp32 (F, W); plan: (in_row int32, tgt_row int32, reset uint8), each (n_steps,); cursor: int32 (2,); inp, tgt: fp32 of W
+    values; state: fp32 or None; status: int32 (1,), zero-filled by the caller ONCE -- a refused step (LSTM_POOL_STATUS) ORs
+    its bit in and writes nothing else; read it back where the loop synchronises and hand it to check_lstm_pool_status.  All
+    tensors contiguous and on the pool's device.  The call reads nothing back, so it can be captured into a hipGraph."""
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.float32 and pool.dim() == 2
+            and pool.is_contiguous() and pool.shape[0] >= 1 and pool.shape[1] >= 1):
+        raise ValueError("lstm_pool_fetch: pool must be a contiguous float32 (F, W) tensor on the GPU")
+    dev = pool.device
+    F, W = pool.shape
+    if W > 4096:
+        raise ValueError(f"lstm_pool_fetch: W = {W}, the loss kernel of the step takes up to 4096 values")
+    if not (isinstance(plan, (tuple, list)) and len(plan) == 3):
+        raise ValueError("lstm_pool_fetch: plan must be (in_row, tgt_row, reset)")
+    in_row, tgt_row, reset = plan
+    for name, t, dt in (("in_row", in_row, torch.int32), ("tgt_row", tgt_row, torch.int32), ("reset", reset, torch.uint8)):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.dim() == 1 and t.is_contiguous()
+                and t.numel() == in_row.numel() and t.numel() >= 1):
+            raise ValueError(f"lstm_pool_fetch: {name} must be a contiguous {dt} (n_steps,) tensor on the pool's device, "
+                             f"n_steps >= 1 and the same for the three plan arrays")
+    if not (isinstance(cursor, torch.Tensor) and cursor.device == dev and cursor.dtype == torch.int32 and cursor.numel() == 2
+            and cursor.is_contiguous()):
+        raise ValueError("lstm_pool_fetch: cursor must be a contiguous int32 tensor of 2 values on the pool's device")
+    for name, t in (("inp", inp), ("tgt", tgt)):
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.numel() == W
+                and t.is_contiguous()):
+            raise ValueError(f"lstm_pool_fetch: {name} must be a contiguous float32 tensor of W = {W} values on the pool's device")
+    if state is not None and not (isinstance(state, torch.Tensor) and state.device == dev and state.dtype == torch.float32
+                                  and state.is_contiguous()):
+        raise ValueError("lstm_pool_fetch: state must be None or a contiguous float32 tensor on the pool's device")
+    if not (isinstance(status, torch.Tensor) and status.device == dev and status.dtype == torch.int32 and status.numel() == 1):
+        raise ValueError("lstm_pool_fetch: status must be an int32 tensor of 1 value on the pool's device")
+    check(LIB.egz_lstm_pool_fetch(pool.data_ptr(), F, W, in_row.data_ptr(), tgt_row.data_ptr(), reset.data_ptr(),
+                                  in_row.numel(), cursor.data_ptr(), inp.data_ptr(), tgt.data_ptr(), _p(state),
+                                  0 if state is None else state.numel(), status.data_ptr(), _stream()), "egz_lstm_pool_fetch")
+
+
 def lstm_cell_fwd(gates, c_prev, h_out, c_out, act):
     B, Hd = c_prev.shape
     check(LIB.egz_lstm_cell_fwd(gates.data_ptr(), c_prev.data_ptr(), h_out.data_ptr(), c_out.data_ptr(), _p(act), B, Hd,

@@ -476,6 +476,19 @@ int egz_resident_gather(const unsigned char* pool, long P, const long* table, lo
  * *status (device, zero-filled by the caller) gets bit 0 (idx) or bit 1 (table). */
 int egz_late_gather(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H, int W,
                     float* fused, float* gt, unsigned char* raw, int* status, hipStream_t stream);
+/* One step of the AT module's LSTM loops fetched from a pool of the extracted fixation vectors that stays on the device
+ * (data/lstm_resident.py, csrc/lstm_pool.hip).  pool (rows, width) fp32; in_row / tgt_row (n_steps,) int32 pool rows and reset
+ * (n_steps,) uint8: the step plan; cursor: two ints on the device, {next step, step being run}.  With k = cursor[0], 0 <= k <
+ * n_steps and both rows of step k inside the pool: inp[0 .. width) = pool[in_row[k]], tgt[0 .. width) = pool[tgt_row[k]],
+ * state[0 .. state_n) = 0 if reset[k] != 0 and state is not null, then cursor[1] = k and cursor[0] = k + 1 -- a later launch of
+ * the same stream can address per-step output off cursor + 1 (egz_mse_fwd_grad's counter).  Otherwise nothing is dereferenced
+ * with the index that failed, nothing is written and the cursor stays: *status (device, zero-filled by the caller once; a sticky
+ * OR) gets bit 0 (cursor outside the plan) or bit 1 (a plan row outside the pool).  One single-block launch; 1 <= width <= 4096
+ * (egz_mse_fwd_grad's limit), rows >= 1, n_steps >= 1, state_n >= 0, every pointer but state required: anything else returns an
+ * error and launches nothing. */
+int egz_lstm_pool_fetch(const float* pool, long rows, int width, const int* in_row, const int* tgt_row,
+                        const unsigned char* reset, long n_steps, int* cursor, float* inp, float* tgt, float* state,
+                        long state_n, unsigned int* status, hipStream_t stream);
 /* AT extraction glue (AT.py:25-39,58-66,229; extractLSTMw.py:81-90): chn_weight = mean of the size x size window of the
  * channels-last (B,H,W,C) feature map around gaze_point / cell; weighted map = min-max normalised sum_c feat * w. */
 int egz_crop_mean(const float* feat, const int* gp, float* out, int B, int H, int W, int C, int size, int cell,
