@@ -1,6 +1,6 @@
 // egz_lstm_pool_fetch (data/lstm_resident.py, `--lstm_resident`): one step of AT.trainLSTM / AT.testLSTM fed from a pool of the
 // extracted fixation vectors that stays in HBM.  The step plan -- which pool row is the input, which the target, and whether the
-// LSTM state is reset first -- is known from the file names before the first step (ResidentLSTMDataset.lstm_plan), so the launch
+// LSTM state is reset first -- is the file loop's own schedule run over the file names (data/lstm_resident.lstm_plan), so the launch
 // takes its step number from a cursor on the device and sits at the head of the step's captured hipGraph: a replay needs nothing
 // from the host.
 //   pool    (rows, width) fp32

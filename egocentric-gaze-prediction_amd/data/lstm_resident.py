@@ -11,26 +11,20 @@ import os
 import numpy as np
 import torch
 
-from .LSTMdatas import lstmDataset
+from .LSTMdatas import deferred_steps, lstmDataset
 
 FILL_THREADS = 16                           # file reads of fill() in flight at most
 
 
 def lstm_plan(listFiles):
     """The steps of one epoch over the sorted file list, from the names alone -> (in_row, tgt_row int32, reset uint8), one entry
-    per step.  AT's loop scores the prediction made from sample i - 1 against the target of sample i, so the forward pass of
-    sample i - 1 is deferred to iteration i (AT._epoch_graphed); sample i is (file i, file i + 1).  Step k = 1 .. F - 2 therefore
-    reads file k - 1 as its input and file k + 1 as its target, and resets the state first where sample k - 1 was flagged
-    ``same == 0`` -- file k - 1 and file k belong to different videos -- or nothing ran before (k = 1).  The flag compares a file
-    with its SUCCESSOR, so the reset falls on the forward pass of the last frame of a video: the reference's quirk, kept."""
-    F = len(listFiles)
-    n = max(F - 2, 0)
-    in_row = np.arange(0, n, dtype=np.int32)
-    tgt_row = np.arange(2, n + 2, dtype=np.int32)
-    reset = np.zeros(n, dtype=np.uint8)
-    for k in range(1, n + 1):
-        reset[k - 1] = k == 1 or listFiles[k][:-14] != listFiles[k - 1][:-14]
-    return in_row, tgt_row, reset
+    per step.  The schedule is LSTMdatas.deferred_steps, the one the file loop runs (AT._epoch_graphed), fed with file rows in
+    place of vectors: sample i is (file i, file i + 1, lstmDataset's ``same`` flag).  Step k = 1 .. F - 2 therefore reads file
+    k - 1 as its input and file k + 1 as its target, and resets the state first where file k - 1 and file k belong to
+    different videos, or nothing ran before (k = 1).  Fewer than three files: no step."""
+    samples = ((i, i + 1, listFiles[i + 1][:-14] == listFiles[i][:-14]) for i in range(len(listFiles) - 1))
+    steps = np.array(list(deferred_steps(samples)), dtype=np.int64).reshape(-1, 3)
+    return steps[:, 0].astype(np.int32), steps[:, 1].astype(np.int32), steps[:, 2].astype(np.uint8)
 
 
 class ResidentLSTMDataset(lstmDataset):

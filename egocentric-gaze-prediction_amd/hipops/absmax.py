@@ -85,7 +85,7 @@ class _AbsmaxArena:
 class capture:
     """``with hipops.capture(graph[, eager_arena=False]): ...`` = ``torch.cuda.graph(graph)`` plus what this package's launches
     need inside a capture: the abs-max arena's per-capture chunk (see _AbsmaxArena).  Every capture site of the package goes
-    through here (graphs.GraphedModule / GraphedTrainStep, AT._GraphedSampleStep)."""
+    through here (graphs.GraphedModule / GraphedTrainStep; AT._GraphedSampleStep, training and validation)."""
 
     def __init__(self, graph, eager_arena: bool = True, **kw):
         self.ctx = torch.cuda.graph(graph, **kw)

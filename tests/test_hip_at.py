@@ -282,6 +282,33 @@ def test_mse_fwd_grad_matches_two_calls():
         assert torch.equal(l0, l2) and torch.equal(d0, d2)
 
 
+def test_loss_ring_drain_returns_parked_losses_and_notices_a_foreign_step():
+    """AT._LossRing, the drain of the graphed training epochs, on a ring of 4 behind a capturable FusedAdam over 8 values: the
+    losses of three steps come back in order, equal to hipops.mse_fwd of the same vectors; an optimizer step the drain was
+    not told about moves the device counter away from the host's count, and the next drain says so (two integers that were
+    read back are compared on the host)."""
+    import egaze_amd.hipops as H
+    from egaze_amd.AT import _LossRing
+    from egaze_amd.optim import FusedAdam
+    opt = FusedAdam([torch.nn.Parameter(torch.zeros(8, device=DEV))], lr=1e-3)
+    opt.set_capturable(True)
+    ring = torch.zeros(4, device=DEV)
+    parked = _LossRing(ring, opt)
+    pairs = [(torch.arange(8.0, device=DEV) * (k + 1) / 8, torch.full((8,), 0.25 * k, device=DEV)) for k in range(3)]
+    for a, b in pairs:
+        H.mse_fwd_grad(a, b, True, ring, opt.step_dev)
+        opt.step()                                          # (the gradient buffer is all zeros: the weights stay)
+        parked.stepped()
+    want = [H.mse_fwd(a, b, True).item() for a, b in pairs]
+    got = parked.drain()
+    print("parked losses:", got, "mse_fwd:", want)
+    assert got == want and len(set(want)) == 3 and parked.pending == 0
+    opt.step()
+    with pytest.raises(RuntimeError, match="out of step"):
+        parked.drain()
+    opt.set_capturable(False)
+
+
 @pytest.mark.parametrize("L,T,B", [(1, 1, 2), (1, 5, 20), (2, 2, 33), (3, 4, 7), (2, 16, 1)])
 def test_lstm_wavefront_vs_torch(L, T, B):
     """egz_lstm_wave_fwd / _bwd (the stacked recurrence as a wavefront over (layer, step)) against torch's nn.LSTM on the CPU, fp64:

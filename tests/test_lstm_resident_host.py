@@ -43,6 +43,39 @@ def walked_plan(ds):
     return np.array(in_row, dtype=np.int32), np.array(tgt_row, dtype=np.int32), np.array(reset, dtype=np.uint8)
 
 
+def test_schedule_of_the_golden_replay_flags():
+    """same = [1, 1, 1, 0, 1] (test_hip_at's replay fixture): four steps, the state reset on the first and on the one whose
+    deferred sample (3) carries the 0."""
+    from egaze_amd.data.LSTMdatas import deferred_steps
+    same = [1, 1, 1, 0, 1]
+    steps = list(deferred_steps((f"in{i}", f"gt{i}", same[i]) for i in range(5)))
+    assert steps == [("in0", "gt1", True), ("in1", "gt2", False), ("in2", "gt3", False), ("in3", "gt4", True)]
+    assert all(type(s[2]) is bool for s in steps)
+
+
+@pytest.mark.parametrize("n", [0, 1])
+def test_schedule_of_fewer_than_two_samples_is_empty(n):
+    from egaze_amd.data.LSTMdatas import deferred_steps
+    assert list(deferred_steps([("in", "gt", 0)] * n)) == []
+
+
+def test_schedule_reads_nothing_ahead():
+    """After yielding k steps the generator has pulled exactly k + 1 samples: the file loop reads no file early."""
+    from egaze_amd.data.LSTMdatas import deferred_steps
+    pulled = []
+
+    def samples():
+        for i in range(6):
+            pulled.append(i)
+            yield i, 10 + i, i != 2
+    steps = deferred_steps(samples())
+    assert pulled == []                                 # nothing before the first step is asked for
+    for k, got in enumerate(steps, start=1):
+        assert len(pulled) == k + 1
+        assert got == (k - 1, 10 + k, k == 1 or k == 3)
+    assert k == 5 and len(pulled) == 6
+
+
 def test_plan_of_the_five_file_example(tmp_path):
     from egaze_amd.data.lstm_resident import ResidentLSTMDataset, lstm_plan
     vector_tree(tmp_path, [("A_x", 3), ("B_x", 2)])

@@ -9,7 +9,6 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import egaze_amd  # noqa
 import egaze_amd.AT as at_mod
-from egaze_amd.functions import MSELoss
 from egaze_amd.models.LSTMnet import lstmnet
 from egaze_amd.optim import FusedAdam
 
@@ -19,7 +18,7 @@ lstm = lstmnet().to(dev)
 lstm.train()
 opt = FusedAdam(lstm.parameters(), lr=1e-4)
 ring = torch.zeros(32, device=dev)
-r = at_mod._GraphedSampleStep(lstm, MSELoss.apply, opt, dev, 512, ring=ring)
+r = at_mod._GraphedSampleStep(lstm, opt, dev, 512, ring)
 pair = torch.rand(2, 512).pin_memory()
 for _ in range(8):
     r.step(pair)
