@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const float* __re
         if (!POOL) {
             const f32x4 v = *reinterpret_cast<const f32x4*>(y + pix * K + c4 * 4);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = fmaxf(v[e] * sc[e] + sh[e], 0.f);
+            for (int e = 0; e < 4; ++e) r[e] = egz_relu(v[e] * sc[e] + sh[e]);
         } else {
             const int xo = (int)(pix % Wo);
             const long t = pix / Wo;
@@ -243,9 +243,9 @@ __global__ __launch_bounds__(256) void bn_relu_pool_fwd_kernel(const float* __re
             const f32x4 v11 = *reinterpret_cast<const f32x4*>(p + (long)W * K + K);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float a = fmaxf(v00[e] * sc[e] + sh[e], v01[e] * sc[e] + sh[e]);
-                const float c = fmaxf(v10[e] * sc[e] + sh[e], v11[e] * sc[e] + sh[e]);
-                r[e] = fmaxf(fmaxf(a, c), 0.f);
+                const float a = egz_max_nan(v00[e] * sc[e] + sh[e], v01[e] * sc[e] + sh[e]);
+                const float c = egz_max_nan(v10[e] * sc[e] + sh[e], v11[e] * sc[e] + sh[e]);
+                r[e] = egz_relu(egz_max_nan(a, c));
             }
         }
         if constexpr (SPLIT) {
@@ -267,12 +267,12 @@ __device__ __forceinline__ void pool_route(const float z[4], float dout, float d
     float bv = z[0];
 #pragma unroll
     for (int q = 1; q < 4; ++q)
-        if (z[q] > bv) {
+        if (z[q] > bv || z[q] != z[q]) {      // (F.max_pool2d: a NaN replaces the running maximum)
             bv = z[q];
             best = q;
         }
 #pragma unroll
-    for (int q = 0; q < 4; ++q) dz[q] = (q == best && bv > 0.f) ? dout : 0.f;
+    for (int q = 0; q < 4; ++q) dz[q] = (q == best && !(bv <= 0.f)) ? dout : 0.f;
 }
 
 // ------------------------------------------------------------------ BN backward, pass 1: per-channel sum(dz), sum(dz*xhat)
@@ -310,7 +310,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float z = v0[e] * sc[e] + sh[e];
-                    const float dz = z > 0.f ? g0[e] : 0.f;
+                    const float dz = z <= 0.f ? 0.f : g0[e];
                     s1[e] += dz;
                     s2[e] += dz * ((v0[e] - mu[e]) * is[e]);
                 }
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const float z = v1[e] * sc[e] + sh[e];
-                        const float dz = z > 0.f ? g1[e] : 0.f;
+                        const float dz = z <= 0.f ? 0.f : g1[e];
                         s1[e] += dz;
                         s2[e] += dz * ((v1[e] - mu[e]) * is[e]);
                     }
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float z = v[e] * sc[e] + sh[e];
-                const float dz = z > 0.f ? g[e] : 0.f;
+                const float dz = z <= 0.f ? 0.f : g[e];
                 const float xh = (v[e] - mu[e]) * is[e];
                 r[e] = sc[e] * (dz - m1[e] - xh * m2[e]);
                 amx = fmaxf(amx, fabsf(r[e]));
@@ -528,13 +528,16 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------ fusion: z = max(ys, yt) (ys wins ties)
+// The first stream wins ties; a NaN wins over a number and the second stream's NaN over the first's -- the scan of
+// nn.MaxPool3d((2, 1, 1)), which replaces its running maximum when the next value is larger or is a NaN.
+__device__ __forceinline__ bool pair_first(float a, float b) { return !(b > a) && b == b; }
 __global__ __launch_bounds__(256) void pairmax_fwd_kernel(const float* __restrict__ y2, float* __restrict__ z, long n4) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const f32x4 a = reinterpret_cast<const f32x4*>(y2)[i];
         const f32x4 b = reinterpret_cast<const f32x4*>(y2)[n4 + i];
         f32x4 r;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = a[e] >= b[e] ? a[e] : b[e];
+        for (int e = 0; e < 4; ++e) r[e] = pair_first(a[e], b[e]) ? a[e] : b[e];
         reinterpret_cast<f32x4*>(z)[i] = r;
     }
 }
@@ -548,7 +551,7 @@ __global__ __launch_bounds__(256) void pairmax_bwd_kernel(const float* __restric
         f32x4 ra, rb;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const bool first = a[e] >= b[e];
+            const bool first = pair_first(a[e], b[e]);
             ra[e] = first ? g[e] : 0.f;
             rb[e] = first ? 0.f : g[e];
             amx = fmaxf(amx, fabsf(g[e]));
@@ -567,7 +570,7 @@ __global__ __launch_bounds__(256) void relu_bwd_kernel(const float* __restrict__
         const f32x4 g = reinterpret_cast<const f32x4*>(dout)[i];
         f32x4 r;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) r[e] = o[e] > 0.f ? g[e] : 0.f;
+        for (int e = 0; e < 4; ++e) r[e] = o[e] <= 0.f ? 0.f : g[e];
         reinterpret_cast<f32x4*>(dy)[i] = r;
     }
 }
@@ -589,7 +592,7 @@ __global__ __launch_bounds__(256) void relu_bwd_bias_kernel(const float* __restr
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                v[e] = o[e] > 0.f ? g[e] : 0.f;
+                v[e] = o[e] <= 0.f ? 0.f : g[e];
                 s[e] += v[e];
                 amx = fmaxf(amx, fabsf(v[e]));
             }
@@ -991,7 +994,7 @@ __global__ __launch_bounds__(256) void bn_bwd_first_wgrad_kernel(
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float z = v[p][e] * sc[e] + sh[e];
-                const float dz = z > 0.f ? g[p][e] : 0.f;
+                const float dz = z <= 0.f ? 0.f : g[p][e];
                 const float xh = (v[p][e] - mu[e]) * is[e];
                 r[e] = sc[e] * (dz - a1[e] - xh * a2[e]);
             }

@@ -243,7 +243,7 @@ __global__ __launch_bounds__(256, (BM == 64) ? 4 : 2) void conv3x3_igemm_kernel(
                 const long off = Ro[wm * WM + mr * 32 + egz_acc_row(r, lane)];
                 if (off >= 0 && nok) {
                     float v = acc[mr][nr][r] + bz;
-                    if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
+                    if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
                     y[off + n0 + col] = v;
                     if (EPI == EPI_BIAS_STATS) {
                         s1 += (double)v;

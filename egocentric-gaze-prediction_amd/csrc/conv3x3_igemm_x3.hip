@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_igemm_x3_kernel(
                 if (bufst) {
                     const bool ok = off >= 0 && nok;
                     float v = acc[mr][nr][r] * out_scale + bz;
-                    if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
+                    if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rs,
                                                           ok ? (unsigned)(off + n0 + col) * 4u : 0xFFFFFFFFu, 0, 0);
                     const float vs = ok ? v : 0.f;
@@ -342,7 +342,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_igemm_x3_kernel(
                 if (off >= 0 && nok) {
                     float v = acc[mr][nr][r] * out_scale + bz;
                     if (EPI == EPI_BIAS_RELU) {
-                        v = fmaxf(v, 0.f);
+                        v = egz_relu(v);
                         amx = fmaxf(amx, v);
                     }
                     y[off + n0 + col] = v;
@@ -667,7 +667,7 @@ __global__ __launch_bounds__(256, (XBN == 64) ? 3 : 2) void conv3x3_igemm_x3h_ke
                 if (bufst) {
                     const bool ok = off >= 0 && nok;
                     float v = acc[mr][nr][r] * out_scale + bz;
-                    if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
+                    if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rs,
                                                           ok ? (unsigned)(off + n0 + col) * 4u : 0xFFFFFFFFu, 0, 0);
                     const float vs = ok ? v : 0.f;
@@ -681,7 +681,7 @@ __global__ __launch_bounds__(256, (XBN == 64) ? 3 : 2) void conv3x3_igemm_x3h_ke
                 if (off >= 0 && nok) {
                     float v = acc[mr][nr][r] * out_scale + bz;
                     if (EPI == EPI_BIAS_RELU) {
-                        v = fmaxf(v, 0.f);
+                        v = egz_relu(v);
                         amx = fmaxf(amx, v);
                     }
                     y[off + n0 + col] = v;

@@ -592,7 +592,7 @@ __global__ __launch_bounds__(Geo<WM>::NTHR, Geo<WM>::OCC) void conv3x3_igemm_x3s
                 const float v = acc[mr][r] * out_scale;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rs, mko[r], 0, 0);
                 const float yp = mkv[r];
-                const float dz = (mko[r] != 0xFFFFFFFFu && yp * csc + csh > 0.f) ? v : 0.f;
+                const float dz = (mko[r] != 0xFFFFFFFFu && !(yp * csc + csh <= 0.f)) ? v : 0.f;
                 amx = fmaxf(amx, fabsf(v));                      // (rows / columns that do not exist hold zeros)
                 q1 += dz;
                 q2 += dz * ((yp - cmu) * cis);
@@ -605,7 +605,7 @@ __global__ __launch_bounds__(Geo<WM>::NTHR, Geo<WM>::OCC) void conv3x3_igemm_x3s
         for (int r = 0; r < 16; ++r) {
             const long off = Ro[wm * RPW + mr * 32 + egz_acc_row(r, lane)];
             if (BUFST && EPI == EPI_MASK_SUMS) {                // (out-of-range lanes read 0: masked, not stored, not summed)
-                const float v = (mkv[r] > 0.f) ? acc[mr][r] * out_scale : 0.f;
+                const float v = (mkv[r] <= 0.f) ? 0.f : acc[mr][r] * out_scale;
                 amx = fmaxf(amx, fabsf(v));
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rs, mko[r], 0, 0);
                 s1 += (double)v;
@@ -618,7 +618,7 @@ __global__ __launch_bounds__(Geo<WM>::NTHR, Geo<WM>::OCC) void conv3x3_igemm_x3s
             if (BUFST) {
                 const bool ok = off >= 0 && nok;
                 float v = acc[mr][r] * out_scale + bz;
-                if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
+                if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rs,
                                                       ok ? (unsigned)(off + col) * 4u : 0xFFFFFFFFu, 0, 0);
                 const float vs = ok ? v : 0.f;
@@ -634,8 +634,8 @@ __global__ __launch_bounds__(Geo<WM>::NTHR, Geo<WM>::OCC) void conv3x3_igemm_x3s
             }
             if (off >= 0 && nok) {
                 float v = acc[mr][r] * out_scale + bz;
-                if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
-                if (EPI == EPI_MASK_SUMS) v = (mask_src[off + col] > 0.f) ? v : 0.f;
+                if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
+                if (EPI == EPI_MASK_SUMS) v = (mask_src[off + col] <= 0.f) ? 0.f : v;
                 if (EPI == EPI_MASK_SUMS || EPI == EPI_BIAS_RELU) amx = fmaxf(amx, fabsf(v));
                 y[off + col] = v;
                 if (EPI == EPI_BIAS_STATS || EPI == EPI_MASK_SUMS) s1 += (double)v;
@@ -990,7 +990,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3p_narrow_kernel(
             if (BNIN) {                                         // BatchNorm + ReLU of the block below, on the way into LDS;
                 const float ms = ((ra_ok >> j) & 1u) ? a_scale : 0.f;      // the zero-padding mask rides on the scale factor
 #pragma unroll
-                for (int e = 0; e < 4; ++e) ra[j][e] = fmaxf(__builtin_fmaf(ra[j][e], in_sc[e], in_sh[e]), 0.f) * ms;
+                for (int e = 0; e < 4; ++e) ra[j][e] = egz_relu(__builtin_fmaf(ra[j][e], in_sc[e], in_sh[e])) * ms;
                 if constexpr (egz_drop_alo<T>::value) hi = Half<T>::rne4s(ra[j], 1.f);
                 else Half<T>::split4(ra[j], hi, lo);
             } else if constexpr (egz_drop_alo<T>::value) {
@@ -1055,7 +1055,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3p_narrow_kernel(
         if (BNIN) {
             const float ms = ((ra_ok >> j) & 1u) ? a_scale : 0.f;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) ra[j][e] = fmaxf(__builtin_fmaf(ra[j][e], in_sc[e], in_sh[e]), 0.f) * ms;
+            for (int e = 0; e < 4; ++e) ra[j][e] = egz_relu(__builtin_fmaf(ra[j][e], in_sc[e], in_sh[e])) * ms;
             if constexpr (egz_drop_alo<T>::value) hi = Half<T>::rne4s(ra[j], 1.f);
             else Half<T>::split4(ra[j], hi, lo);
         } else if constexpr (egz_drop_alo<T>::value) {
@@ -1102,7 +1102,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3p_narrow_kernel(
         float q1 = 0.f, q2 = 0.f;
         auto epi_elem = [&](const int mr, const int r) {
             float v = pacc[mr][r] * out_scale + pbz;
-            if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
+            if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), py_rs, o_vo[mr][r], pso, 0);
             if (EPI == EPI_BIAS_STATS) {                       // (fp64 per element: the variance is a difference of the two sums)
                 s1 += (double)v;
@@ -1112,7 +1112,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3p_narrow_kernel(
             }
             if (EPI == EPI_BNSUMS) {
                 const float yp = byp[mr][r];
-                const float dz = (yp * bn_sc + bn_sh > 0.f) ? v : 0.f;
+                const float dz = (yp * bn_sc + bn_sh <= 0.f) ? 0.f : v;
                 q1 += dz;
                 q2 += dz * ((yp - bn_mu) * bn_is);
             }
@@ -1186,7 +1186,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3p_narrow_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 float v = pacc[mr][r] * out_scale + bz;
-                if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.f);
+                if (EPI == EPI_BIAS_RELU) v = egz_relu(v);
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), y_rs, o_vo[mr][r], pso, 0);
                 if (EPI == EPI_BIAS_STATS) {
                     s1 += (double)v;
@@ -1196,7 +1196,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_x3p_narrow_kernel(
                 }
                 if (EPI == EPI_BNSUMS) {
                     const float yp = byp[mr][r];
-                    const float dz = (yp * bn_sc + bn_sh > 0.f) ? v : 0.f;
+                    const float dz = (yp * bn_sc + bn_sh <= 0.f) ? 0.f : v;
                     q1 += dz;
                     q2 += dz * ((yp - bn_mu) * bn_is);
                 }
@@ -1320,7 +1320,7 @@ __global__ __launch_bounds__(256) void splitk_fixup_kernel(const float* __restri
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 if (EPI == EPI_BIAS_RELU) {
-                    v[e] = fmaxf(v[e], 0.f);
+                    v[e] = egz_relu(v[e]);
                     amx = fmaxf(amx, v[e]);
                 }
                 if (EPI == EPI_BIAS_STATS) {

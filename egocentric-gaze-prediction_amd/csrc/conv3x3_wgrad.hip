@@ -721,7 +721,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3n_kernel(
                 if (BNIN) {                                     // BatchNorm + ReLU of the block below, on the way into LDS;
                     const float ms = ((rx_ok >> j) & 1u) ? x_scale : 0.f;  // the zero-padding mask rides on the scale factor
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) rx[j][e] = fmaxf(__builtin_fmaf(rx[j][e], in_sc[e], in_sh[e]), 0.f) * ms;
+                    for (int e = 0; e < 4; ++e) rx[j][e] = egz_relu(__builtin_fmaf(rx[j][e], in_sc[e], in_sh[e])) * ms;
                     if constexpr (egz_drop_alo<T>::value) f16_rne4(rx[j], hi);
                     else W16<T>::split4(rx[j], hi, lo);
                 } else if constexpr (egz_drop_alo<T>::value) {
@@ -914,7 +914,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wgrad9_x3t_kernel(
             if (BNIN) {
                 const float ms = ((rx_ok >> j) & 1u) ? x_scale : 0.f;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) rx[j][e] = fmaxf(__builtin_fmaf(rx[j][e], in_sc[e], in_sh[e]), 0.f) * ms;
+                for (int e = 0; e < 4; ++e) rx[j][e] = egz_relu(__builtin_fmaf(rx[j][e], in_sc[e], in_sh[e])) * ms;
                 if constexpr (egz_drop_alo<T>::value) f16_rne4(rx[j], hi);
                 else W16<T>::split4(rx[j], hi, lo);
             } else if constexpr (egz_drop_alo<T>::value) {

@@ -65,7 +65,18 @@ inline auto by_bool(bool b) { return [b](auto&& k) { if (b) k(std::true_type{});
 
 // 32x32 accumulator element `reg` of lane `lane` sits at row (reg&3)+8*(reg>>2)+4*(lane>>5),
 // column lane&31 (cdna_hip_programming.md section 3; dtype-independent on gfx950).
-__device__ __forceinline__ int egz_acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }// Abs-max buffer of a tensor (egz_absmax_elems() uints, ZERO-FILLED by the caller before the producing launch): EGZ_AM_SLOTS slots,
+__device__ __forceinline__ int egz_acc_row(int reg, int lane) { return (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5); }
+
+// ReLU and maximum that PROPAGATE a NaN, as torch.relu, F.max_pool2d and torch.maximum do (fmaxf returns the operand that is a
+// number, so fmaxf(NaN, 0) is 0: a diverged channel would turn into a dead one and the loss would stay finite).  Every ReLU, the
+// 2x2 pool and the fusion pair-max go through these two, so that a NaN that entered a step is still a NaN in the loss that is read
+// back and in every gradient (FusedAdam skips those elements and raises its flag).  One instruction on gfx950 (IEEE-754-2019
+// maximum).  The abs-max REDUCTIONS keep fmaxf on purpose: a NaN element stays NaN through the f16 split whatever the scale is,
+// and the scale of every other element stays right.
+__device__ __forceinline__ float egz_relu(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+__device__ __forceinline__ float egz_max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
+// Abs-max buffer of a tensor (egz_absmax_elems() uints, ZERO-FILLED by the caller before the producing launch): EGZ_AM_SLOTS slots,
 // one per 128-byte line (index slot * EGZ_AM_STRIDE), each holding the bit pattern of a non-negative float.  A producing
 // block folds its own maximum into slot (block index % EGZ_AM_SLOTS) with ONE device-scope atomic max -- skipped when the slot
 // already holds a larger value, so a launch of thousands of blocks issues a few dozen atomics, spread over 32 lines; bit patterns

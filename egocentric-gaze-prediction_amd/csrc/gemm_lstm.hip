@@ -76,7 +76,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(const float* __restrict__ A, 
             if (m < M) {
                 float v = acc[r] + bz;
                 if (flags & 1) v += C[(long)m * ldc + n];
-                if (flags & 2) v = fmaxf(v, 0.f);
+                if (flags & 2) v = egz_relu(v);
                 C[(long)m * ldc + n] = v;
             }
         }
@@ -176,7 +176,7 @@ __device__ __forceinline__ void gemm_fast_body(const float* __restrict__ A, cons
         const int m = m0 + wm * 32 + egz_acc_row(r, lane);
         float v = acc[r] + bz;
         if (flags & 1) v += C[(long)m * ldc + n];
-        if (flags & 2) v = fmaxf(v, 0.f);
+        if (flags & 2) v = egz_relu(v);
         C[(long)m * ldc + n] = v;
     }
 }

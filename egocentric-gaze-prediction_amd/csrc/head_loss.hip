@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void conv1x1_sigmoid_bwd_kernel(const float* _
             for (int e = 0; e < 4; ++e) {
                 r[e] = dl * wv[e];
                 if (MASK) {
-                    r[e] = v[e] > 0.f ? r[e] : 0.f;
+                    r[e] = v[e] <= 0.f ? 0.f : r[e];      // (torch's threshold_backward: a NaN activation passes its gradient)
                     ms[e] += r[e];
                     amx = fmaxf(amx, fabsf(r[e]));
                 }
@@ -215,8 +215,8 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ 
             weights[i] = wgt;
         }
         const float x = inp[i], t = target[i];
-        const float lx = fmaxf(logf(x), -100.f);
-        const float l1x = fmaxf(log1pf(-x), -100.f);
+        const float lx = egz_max_nan(logf(x), -100.f);          // (torch clamps with clamp_min, which keeps a NaN)
+        const float l1x = egz_max_nan(log1pf(-x), -100.f);
         const float l = ((t - 1.f) * l1x - t * lx) * wgt;
         acc += (double)l;
     }

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void lin_relu_b1_kernel(const float* __restric
         s += wv[0] * hv[0] + wv[1] * hv[1] + wv[2] * hv[2] + wv[3] * hv[3];
     }
     s = wave_sum(s);
-    if (lane == 0) out[i] = fmaxf(s + b[i], 0.f);
+    if (lane == 0) out[i] = egz_relu(s + b[i]);
 }
 
 constexpr int STRIP = 8;      // rows of a weight matrix per backward block (128 threads x 4 columns each)
@@ -108,7 +108,7 @@ __global__ __launch_bounds__(128) void outer_b1_kernel(const float* __restrict__
         float v = 0.f;
         if (r < R) {
             v = d[r];
-            if (relu_out && !(relu_out[r] > 0.f)) v = 0.f;
+            if (relu_out && relu_out[r] <= 0.f) v = 0.f;      // (a NaN output passes its gradient, as torch's ReLU backward)
             if (db) db[r] = v;
             if (db2) db2[r] = v;
         }

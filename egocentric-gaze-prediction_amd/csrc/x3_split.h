@@ -20,7 +20,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <typename T> struct Half;
 template <> struct Half<_Float16> {
     static __device__ __forceinline__ void split(float x, unsigned short& h, unsigned short& l) {
-        x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
+        // (saturate what is finite and out of range; a NaN or inf weight stays one -- v_med3_f32 would return a finite bound for a
+        //  NaN and the poisoned filter would compute on as if nothing had happened)
+        if (fabsf(x) < INFINITY) x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
         const _Float16 hi = (_Float16)x;
         const _Float16 lo = (_Float16)(x - (float)hi);
         h = __builtin_bit_cast(unsigned short, hi);
