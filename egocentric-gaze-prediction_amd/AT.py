@@ -164,7 +164,11 @@ class _GraphedSampleStep:
 
     ``optimizer=None``: a step of AT.testLSTM's loop, captured under the caller's torch.no_grad() -- the same unit without
     zero_grad / backward / Adam.  The loss kernel stays hipops.mse_fwd_grad (its gradient output is discarded, its loss is
-    bit-identical with hipops.mse_fwd's, csrc/head_loss.hip) because it can park the loss itself."""
+    bit-identical with hipops.mse_fwd's, csrc/head_loss.hip) because it can park the loss itself.
+
+    Unlike graphs.GraphedTrainStep a replay here repeats no host-side write declaration (hipops.note_replay): the LSTM path
+    reads its nn.Parameters directly (GEMM and gate kernels on the flat buffer's views) -- no packed copy, BatchNorm fold or eval
+    row keyed by hipops.packing._tag exists for them, so nothing host-side can go stale behind a replay."""
     WARM = 3
 
     def __init__(self, lstm, optimizer, device, width, ring, counter=None, fetch=None):

@@ -1142,10 +1142,14 @@ EGZ_API int egz_pairmax_bwd(const float* y2, const float* dz, float* dy2, long n
 // `absmax` / `absmax_out` buffer folds this reduction into its own pass and expects the buffer ZERO-FILLED by the caller; this one
 // serves callers that hold a bare tensor and zero-fills the buffer itself (stream-ordered).  n must be a multiple of 4.
 EGZ_API int egz_absmax_elems(void) { return EGZ_AM_SLOTS * EGZ_AM_STRIDE; }
+EGZ_API int egz_fill_zero(void* dst, size_t bytes, hipStream_t st);
 EGZ_API int egz_absmax(const float* x, long n, unsigned int* absmax, hipStream_t st) {
     EGZ_CHECK_ARG(x && absmax && n > 0 && n % 4 == 0, "egz_absmax: bad arguments");
-    hipError_t e = hipMemsetAsync(absmax, 0, sizeof(unsigned int) * EGZ_AM_SLOTS * EGZ_AM_STRIDE, st);
-    if (e != hipSuccess) { egz_set_error("egz_absmax: memset failed: %s", hipGetErrorString(e)); return (int)e; }
+    // zero-filled by a KERNEL (egz_fill_zero on a 16-byte aligned buffer), not by hipMemsetAsync: captured into a hipGraph the
+    // runtime's memset node was seen to land out of order with the reduction below on replays that follow eager launches
+    // (max |x| read back as a stale or zero value: tests/test_hip_graph_replay.py, the stream pattern)
+    const int e = egz_fill_zero(absmax, sizeof(unsigned int) * EGZ_AM_SLOTS * EGZ_AM_STRIDE, st);
+    if (e != 0) return e;
     hipLaunchKernelGGL(absmax_kernel, dim3(ew_grid(n / 4)), dim3(256), 0, st, x, n / 4, absmax);
     EGZ_CHECK_LAUNCH("egz_absmax");
     return 0;

@@ -72,9 +72,11 @@ class GraphedTrainStep:
     optimizer must be a FusedAdam (its step counter moves to the device).  Inside the capture every weight-gradient fork joins
     back (functions._close_fork), BatchNorm running statistics and ``num_batches_tracked`` are updated by kernels, so a replay
     is exactly one eager step.  The first ``warm`` calls run eagerly (real steps: lazy packings, workspaces and helper
-    streams come into being), the next one is captured.  A replay moves no host-side version or epoch: evaluate between two
-    replays of one step object only after ``H.touch_params`` on the model's parameters and buffers ("Writes
-    behind torch's back").
+    streams come into being), the next one is captured.  The capture logs what the step declares written behind torch's back
+    (``H.touch_params``: FusedAdam.step, bn_finalize*) and which packings it rebuilds after that; after every replay the step
+    object repeats those declarations on the host (``H.note_replay``: no launch), so an eval forward, a BatchNorm fold or a
+    graphs.GraphedModule between two replays of one step object sees the new weights and running statistics without help
+    (INTEGRATION.md, "Writes behind torch's back"; tests/test_hip_graph_replay.py).
 
     For single-chain models (late_fusion, lstmnet, the stream pre-training VGG: streamtrain.GraphedStreamStep).  The two-stream
     SP step is NOT capturable this way -- its encoder streams and
@@ -112,10 +114,13 @@ class GraphedTrainStep:
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             count = self.opt.step_count
-            with H.capture(g):
+            cap = H.capture(g)
+            with cap:
                 self._unit()
             self.opt.step_count = count          # the capture ran the host side of step() without executing anything
             self.graph = g
+            # (the declarations that ran on the host during the capture stand for this call's replay)
+            self._written, self._rebuilt = cap.written, cap.rebuilt
             self._tags = [H._tag(p) for p in self.opt.params]
             self._extra_sig = self._extra_signature()
             g.replay()
@@ -124,8 +129,8 @@ class GraphedTrainStep:
             # the captured step rebuilds the packed weights AFTER its Adam update (FusedAdam.step -> H.refresh_packings), so its
             # forward pass trusts them: parameters overwritten from outside between two replays must be repacked here.  The
             # full tag is compared: the version counter sees load_state_dict and copy_, the per-parameter and the global epoch
-            # see the writes torch cannot (``p.data.copy_`` + H.touch_params, H.bump_weight_epoch; a replay itself moves none
-            # of them -- the captured step's own touch_params ran on the host once, at capture time)
+            # see the writes torch cannot (``p.data.copy_`` + H.touch_params, H.bump_weight_epoch).  The replay's own writes are
+            # declared by _declared() below, which re-reads the tags: they are not taken for a write from outside here
             tags = [H._tag(p) for p in self.opt.params]
             if tags != self._tags:
                 H.refresh_packings(self.opt.params, force=True)      # the fragment-ordered packings, one launch
@@ -143,7 +148,17 @@ class GraphedTrainStep:
                     self._extra_sig = sig
             self.graph.replay()
             self.opt.note_replays(1)
+            self._declared()
         return self.out
+
+    def _declared(self):
+        """The host side of what the replay just wrote on the device: the per-tensor epochs of the Adam parameters and the
+        BatchNorm running means move as in an eager step, the packings the graph rebuilt carry the new tag, and the step's own
+        reference tags follow.  Host only (tests/test_hip_graph_replay.py counts the launches)."""
+        H.note_replay(self._written, self._rebuilt)
+        self._tags = [H._tag(p) for p in self.opt.params]
+        if self.extra:
+            self._extra_sig = self._extra_signature()
 
     def _extra_signature(self):
         """(what says the values changed, the addresses): the full tag of every extra parameter, the global epoch included --

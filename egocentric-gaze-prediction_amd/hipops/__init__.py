@@ -96,8 +96,8 @@ from ._core import (  # noqa: E402,F401
     _req, _stream, workspace,
 )
 from .packing import (  # noqa: E402,F401
-    _BATCH_PINNED, _BATCH_TABLES, _PACKED, _PACK_FN, _UID, _USED, _WEIGHT_EPOCH, _drop_packed, _tag, _uid,
-    bump_weight_epoch, packed_weight, refresh_packings, repack_stale, touch_params,
+    _BATCH_PINNED, _BATCH_TABLES, _CAPTURE_LOG, _PACKED, _PACK_FN, _UID, _USED, _WEIGHT_EPOCH, _drop_packed, _tag, _uid,
+    bump_weight_epoch, note_replay, packed_weight, refresh_packings, repack_stale, touch_params,
 )
 from .sinks import (  # noqa: E402,F401
     GradSink, PENDING_PRODUCER, grad_done, grad_sink,

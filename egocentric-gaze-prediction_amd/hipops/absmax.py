@@ -85,11 +85,14 @@ class _AbsmaxArena:
 class capture:
     """``with hipops.capture(graph[, eager_arena=False]): ...`` = ``torch.cuda.graph(graph)`` plus what this package's launches
     need inside a capture: the abs-max arena's per-capture chunk (see _AbsmaxArena).  Every capture site of the package goes
-    through here (graphs.GraphedModule / GraphedTrainStep; AT._GraphedSampleStep, training and validation)."""
+    through here (graphs.GraphedModule / GraphedTrainStep; AT._GraphedSampleStep, training and validation).
+    After the block ``written`` holds the tensors the captured launches were declared to write (hipops.touch_params: the fused
+    optimizer's parameters, BatchNorm running means) and ``rebuilt`` the keys of the packings they rebuild: hipops.note_replay."""
 
     def __init__(self, graph, eager_arena: bool = True, **kw):
         self.ctx = torch.cuda.graph(graph, **kw)
         self.eager_arena = eager_arena
+        self.written, self.rebuilt = [], []
 
     def __enter__(self):
         # the persistent LSTM launches keep their hand-off scratch per (device, stream), zeroed ONCE when it is allocated (its
@@ -106,9 +109,16 @@ class capture:
             _H.ABSMAX_ARENA.capture_end()
             self.ctx.__exit__(None, None, None)
             raise
+        _H._CAPTURE_LOG[0] = ([], [])
         return self
 
     def __exit__(self, *exc):
+        # what the captured launches write behind torch's back, and the packings they rebuild after it: the host side of those
+        # declarations ran once, here; the owner of the graph repeats it after every replay (hipops.note_replay)
+        log, _H._CAPTURE_LOG[0] = _H._CAPTURE_LOG[0], None
+        if log is not None:
+            self.written = list({id(t): t for t in log[0]}.values())
+            self.rebuilt = list(dict.fromkeys(log[1]))
         _H.ABSMAX_ARENA.capture_end()
         return self.ctx.__exit__(*exc)
 

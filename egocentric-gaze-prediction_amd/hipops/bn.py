@@ -28,7 +28,7 @@ def bn_finalize(stat: torch.Tensor, count: float, gamma, beta, running_mean, run
     coef = torch.empty((4, K), dtype=torch.float32, device=dev)      # mean, invstd, scale, shift
     ws = _H.workspace(LIB.egz_bn_ws_bytes(K), dev)
     if running_mean is not None:        # written behind torch's back: invalidate what is cached on it (bn_eval_coeffs)
-        running_mean._egz_epoch = getattr(running_mean, "_egz_epoch", 0) + 1
+        _H.touch_params((running_mean,))
     args = (stat.data_ptr(), rows, K, float(count), _p(gamma), _p(beta), _p(running_mean), _p(running_var), momentum, eps,
             coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(), coef[3].data_ptr(), _p(num_batches_tracked),
             ws.data_ptr(), ws.numel())
@@ -71,7 +71,7 @@ def bn_finalize_deferred(stat: torch.Tensor, minmax: torch.Tensor, count: float,
     coef = torch.empty((4, K), dtype=torch.float32, device=dev)
     am = _new_absmax(dev)
     if running_mean is not None:
-        running_mean._egz_epoch = getattr(running_mean, "_egz_epoch", 0) + 1
+        _H.touch_params((running_mean,))
     check(LIB.egz_bn_finalize_deferred(stat.data_ptr(), rows, K, float(count), _p(gamma), _p(beta), _p(running_mean),
                                        _p(running_var), momentum, eps, coef[0].data_ptr(), coef[1].data_ptr(),
                                        coef[2].data_ptr(), coef[3].data_ptr(), _p(num_batches_tracked), minmax.data_ptr(),

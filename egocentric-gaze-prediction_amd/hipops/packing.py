@@ -33,6 +33,28 @@ def touch_params(params):
     address, so nothing else can see it."""
     for p in params:
         p._egz_epoch = getattr(p, "_egz_epoch", 0) + 1
+    log = _CAPTURE_LOG[0]
+    if log is not None:             # inside hipops.capture(): every replay of the graph writes these again (note_replay)
+        log[0].extend(params)
+
+
+# While ``hipops.capture()`` is open: [tensors declared written (touch_params: FusedAdam.step, bn_finalize*), keys of the packings
+# the captured launches rebuild (refresh_packings)].  The host side of a captured step runs once; its kernels run on every replay.
+_CAPTURE_LOG = [None]
+
+
+def note_replay(written, rebuilt):
+    """After ``graph.replay()`` of a capture that logged ``written`` / ``rebuilt`` (``hipops.capture.written`` / ``.rebuilt``):
+    declare the replay's device-side writes the way the eager step does (the per-tensor epoch: eval rows, BatchNorm folds, eval-only
+    packing kinds and graphs.GraphedModule go stale), and stamp the packings the replay itself rebuilt AFTER those writes with the
+    new tag (they are fresh).  Host only: no launch, no synchronisation."""
+    for p in written:
+        p._egz_epoch = getattr(p, "_egz_epoch", 0) + 1
+    for key in rebuilt:
+        hit = _PACKED.get(key)
+        w = hit[2]() if hit is not None else None
+        if w is not None:
+            _PACKED[key] = (_tag(w), hit[1], hit[2])
 
 
 def _tag(w):
@@ -149,9 +171,12 @@ def refresh_packings(params, force: bool = False) -> int:
         if capturing:
             _BATCH_PINNED.add(sig)
         check(LIB.egz_pack_w3x3_frag_batch(ent[0].data_ptr(), len(todo), ent[1], _stream()), "egz_pack_w3x3_frag_batch")
+    log = _CAPTURE_LOG[0]
     for key, w, buf in todo:
         _PACKED[key] = (_tag(w), buf, weakref.ref(w))
         _USED.discard(key)
+        if capturing and log is not None:
+            log[1].append(key)
     return len(todo)
 
 
