@@ -13,6 +13,7 @@
 //   out = rint(fl64(fl64(h * 0.3) + fl64(i * 0.5)))
 // Every operation is a separate IEEE operation: contraction into FMA is off for this file (build.sh flags unchanged).
 #include "egz_common.h"
+#include "linear_u8.h"
 
 #pragma clang fp contract(off)
 
@@ -20,18 +21,7 @@ namespace {
 
 constexpr int NT = 256;
 
-// One 8-bit channel sample of INTER_LINEAR at output (dy, dx); plane = the source channel's first byte, pitch = bytes between
-// two source rows, step = bytes between two horizontally adjacent samples of the channel (1 planar, C interleaved).
-__device__ __forceinline__ int linear_sample(const unsigned char* __restrict__ plane, long pitch, int step, int sh, int sw,
-                                             int sx, int a0, int a1, int sy, int b0, int b1) {
-    const int x1 = min(sx + 1, sw - 1);
-    const int r0 = min(max(sy, 0), sh - 1), r1 = min(max(sy + 1, 0), sh - 1);
-    const unsigned char* p0 = plane + r0 * pitch;
-    const unsigned char* p1 = plane + r1 * pitch;
-    const int S0 = (int)p0[(long)sx * step] * a0 + (int)p0[(long)x1 * step] * a1;
-    const int S1 = (int)p1[(long)sx * step] * a0 + (int)p1[(long)x1 * step] * a1;
-    return (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
-}
+// (linear_sample: one 8-bit channel sample of INTER_LINEAR, linear_u8.h)
 
 // grid (ceil(dh * dw / NT), N); one thread per output pixel, all C channels
 __global__ __launch_bounds__(NT) void resize_linear_u8_kernel(const unsigned char* __restrict__ src, int C, int sh, int sw,

@@ -7,7 +7,7 @@ Activations are NHWC fp32 (``(B, H, W, C)`` contiguous tensors); weights keep th
 All wrappers raise on CPU tensors -- there is no CPU fallback.
 
 One module per op family (``_core``, ``packing``, ``sinks``, ``absmax``, ``conv``, ``bn``, ``layout``, ``loss``, ``lstm``,
-``metrics``, ``dataprep``, ``jpeg``, ``vis``, ``flow``); every name is re-exported here, and callers use ``hipops.NAME``.
+``metrics``, ``dataprep``, ``jpeg``, ``vis``, ``flow``, ``handover``); every name is re-exported here, and callers use ``hipops.NAME``.
 
 This file holds the SWITCHES: every name that a driver or a test rebinds on this module (``hipops.PRECISION = "f32"``,
 ``monkeypatch.setattr(hipops, "SPLITK", False)``).  The family modules never bind them; they read ``_H.NAME`` (``_H`` = this
@@ -150,3 +150,4 @@ from .flow import (  # noqa: E402,F401
     bgr_to_gray_u8, flow_gauss, flow_grad, flow_level_sizes, flow_pyramid_sigma, flow_resample, flow_to_u8,
     tvl1_flow, tvl1_iterate, tvl1_warp,
 )
+from .handover import LATE_INPUT_STATUS, _map_dev, draw_ring, late_input, late_input_status  # noqa: E402,F401

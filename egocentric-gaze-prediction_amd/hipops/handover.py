@@ -1,0 +1,117 @@
+"""The AT -> LF hand-over on the device (late_input) and the gaze marker of an overlay (draw_ring): predict.py's glue."""
+from __future__ import annotations
+
+import sys
+from typing import Optional
+
+import torch
+
+from .._lib import check
+from ._core import LIB, _p, _stream
+
+_H = sys.modules[__package__]      # the package: switches and public functions are read through it at call time
+
+LATE_INPUT_STATUS = {1: "a NaN was quantised to 0", 2: "a value outside [0, 1] was clamped",
+                     3: "a NaN was quantised to 0 and a value outside [0, 1] was clamped"}
+
+
+def _map_dev(t, name, what):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a HIP ('cuda') tensor -- this package has no CPU path")
+    if t.dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"{what}: {name} must be float32 or uint8, got {t.dtype}")
+    if t.dim() != 3 or min(t.shape) == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty (B, H, W), got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
+    return t
+
+
+def late_input(sp: torch.Tensor, at: torch.Tensor, want_u8: bool = False, status_to: Optional[dict] = None):
+    """late_fusion's input from the SP map and the AT map of a batch, as AT.extract_late's files and data.lateDataset would
+    hand it over, in one launch (egz_late_input).
+
+    sp: (B, H, W) fp32 SP map, or uint8 (already quantised); at: (B, h, w) fp32 AT map (weighted_minmax's output), or uint8;
+    contiguous, on one GPU.  fp32 values are quantised as ``(255 * x).to(torch.uint8)`` (truncation), the AT plane at h x w and
+    then resized to H x W with resize_linear_u8's arithmetic (cv2.resize, INTER_LINEAR).  -> fused (B, 2, H, W) fp32, channel 0
+    the AT plane / 255 and channel 1 the SP plane / 255 -- LF.trainLate's order, bit-identical with late_gather of the same
+    planes; with ``want_u8`` also planes (B, 2, H, W) uint8 in the same order.  NaN or x < 0 gives 0, 255 x >= 256 gives 255 (a
+    NaN AT map is legitimate: weighted_minmax of a constant map is 0 / 0).  The launch's status word (bit 0: NaN, bit 1: out
+    of range) is handled as late_gather's: read here (a wait for this launch; a non-zero word warns, the outputs are defined), or,
+    with ``status_to`` (a dict), left there as ``(pinned host word, event)`` under '_late_input_status' for late_input_status."""
+    what = "late_input"
+    _map_dev(sp, "sp", what)
+    _map_dev(at, "at", what)
+    if sp.device != at.device:
+        raise ValueError(f"{what}: sp and at must be on one device ({sp.device} vs {at.device})")
+    if sp.shape[0] != at.shape[0]:
+        raise ValueError(f"{what}: {sp.shape[0]} SP maps but {at.shape[0]} AT maps")
+    B, Hh, Ww = (int(v) for v in sp.shape)
+    h, w = int(at.shape[1]), int(at.shape[2])
+    if B > 65535:
+        raise ValueError(f"{what}: {B} samples in one launch (65535 at most)")
+    if B * 2 * Hh * Ww * 4 >= 1 << 32:
+        raise ValueError(f"{what}: a fused output of {B * 2 * Hh * Ww * 4} bytes; below 4 GiB per launch")
+    dev = sp.device
+    tabs = (None,) * 4 if (h, w) == (Hh, Ww) else _H._linear_tables(dev, (h, w), (Hh, Ww), what)
+    fused = torch.empty((B, 2, Hh, Ww), dtype=torch.float32, device=dev)
+    planes = torch.empty((B, 2, Hh, Ww), dtype=torch.uint8, device=dev) if want_u8 else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_late_input(sp.data_ptr(), int(sp.dtype == torch.uint8), at.data_ptr(), int(at.dtype == torch.uint8), B, Hh, Ww,
+                             h, w, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]), fused.data_ptr(), _p(planes),
+                             status.data_ptr(), _stream()), "egz_late_input")
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_late_input_status'] = (host, done)
+    else:
+        st = _H.late_input_status((host, done))
+        if st:
+            import warnings
+            warnings.warn(f"late_input: {LATE_INPUT_STATUS.get(st, st)}", RuntimeWarning, stacklevel=2)
+    return (fused, planes) if want_u8 else fused
+
+
+def late_input_status(pending) -> int:
+    """Waits for the late_input launch that ``pending = (host status word, event)`` belongs to -> its status word (0: every
+    value was inside [0, 1]; LATE_INPUT_STATUS names the bits).  Nothing was skipped: the outputs are defined either way."""
+    host, ev = pending
+    ev.synchronize()
+    return int(host[0])
+
+
+def draw_ring(images: torch.Tensor, centers: torch.Tensor, r_in: int, r_out: int, colour=(255, 255, 255)) -> torch.Tensor:
+    """A ring (r_in = 0: a disc) drawn into M images in place, one launch (egz_draw_ring).
+
+    images: (M, H, W, 3) uint8, contiguous, on the GPU (BGR as everywhere here); centers: (M, 2) int32 (row, col) on the same
+    GPU, inside the image or not (the ring is clipped); 0 <= r_in <= r_out integers; colour: three bytes in the images' channel
+    order.  Pixel (y, x) takes the colour iff r_in^2 <= (y - cy)^2 + (x - cx)^2 <= r_out^2, in integers.  -> images."""
+    what = "draw_ring"
+    if not isinstance(images, torch.Tensor) or not isinstance(centers, torch.Tensor):
+        raise ValueError(f"{what}: images and centers must be tensors")
+    if not images.is_cuda or not centers.is_cuda or images.device != centers.device:
+        raise ValueError(f"{what}: images and centers must be HIP ('cuda') tensors on one device -- this package has no CPU path")
+    if images.dtype != torch.uint8 or images.dim() != 4 or images.shape[3] != 3 or min(images.shape) == 0:
+        raise ValueError(f"{what}: images must be a non-empty uint8 (M, H, W, 3), got {images.dtype} {tuple(images.shape)}")
+    if centers.dtype != torch.int32 or tuple(centers.shape) != (images.shape[0], 2):
+        raise ValueError(f"{what}: centers must be int32 ({images.shape[0]}, 2), got {centers.dtype} {tuple(centers.shape)}")
+    if not images.is_contiguous() or not centers.is_contiguous():
+        raise ValueError(f"{what}: images and centers must be contiguous")
+    for name, v in (("r_in", r_in), ("r_out", r_out)):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"{what}: {name} must be an integer, got {v!r}")
+    if not 0 <= r_in <= r_out < 1 << 30:
+        raise ValueError(f"{what}: radii {r_in} .. {r_out}: 0 <= r_in <= r_out is needed")
+    col = tuple(int(c) for c in colour)
+    if len(col) != 3 or any(not 0 <= c <= 255 for c in col):
+        raise ValueError(f"{what}: colour {colour!r} must be three values in 0 .. 255")
+    M, Hh, Ww = (int(v) for v in images.shape[:3])
+    if M > 65535:
+        raise ValueError(f"{what}: {M} images in one launch (65535 at most)")
+    check(LIB.egz_draw_ring(images.data_ptr(), M, Hh, Ww, centers.data_ptr(), r_in, r_out, col[0], col[1], col[2], _stream()),
+          "egz_draw_ring")
+    return images

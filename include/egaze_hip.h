@@ -419,6 +419,22 @@ int egz_heatmap_overlay(const unsigned char* maps, int M, int h, int w, const in
                         const short* yalpha, unsigned char* out, hipStream_t stream);
 int egz_cell_argmax_u8(const unsigned char* gt, int N, int H, int W, int cell, int* out, hipStream_t stream);
 
+/* The AT -> LF hand-over on the device and the gaze marker of an overlay (predict.py, csrc/late_input.hip).
+ * late_input: sp (B, H, W) and at (B, h, w) are fp32 maps, or uint8 planes where sp_u8 / at_u8 is non-zero.  An fp32 value is
+ * quantised as q = trunc(fl32(255 x)) -- (255 * x).to(uint8) for x in [0, 1]; NaN or x < 0 gives 0 and 255 x >= 256 gives 255,
+ * and *status (device, zero-filled by the caller) gets bit 0 (NaN) or bit 1 (out of range).  The AT plane is quantised at h x w
+ * and resized to H x W with egz_resize_linear_u8's arithmetic and tables (all four null when (h, w) == (H, W): no resize).
+ * fused (B, 2, H, W) fp32: channel 0 the AT plane, channel 1 the SP plane, every value (float)u8 / 255.f -- bit-identical
+ * with egz_late_gather of the same planes; planes (B, 2, H, W) uint8, optional (null: not written), the same two planes.
+ * fused stays below 4 GiB.  No allocation, no synchronisation.
+ * draw_ring: images (M, H, W, 3) uint8 in place; pixel (y, x) of image m takes (c0, c1, c2) iff
+ * r_in^2 <= (y - centers[2m])^2 + (x - centers[2m + 1])^2 <= r_out^2 (integers); centres may lie outside the image. */
+int egz_late_input(const void* sp, int sp_u8, const void* at, int at_u8, int B, int H, int W, int h, int w, const int* xofs,
+                   const short* xalpha, const int* yofs, const short* yalpha, float* fused, unsigned char* planes, int* status,
+                   hipStream_t stream);
+int egz_draw_ring(unsigned char* images, int M, int H, int W, const int* centers, int r_in, int r_out, int c0, int c1, int c2,
+                  hipStream_t stream);
+
 /* Baseline JPEG decode of N streams in one call (data/STdatas.STDataset(decode='gpu'), csrc/jpeg_decode.hip): stream i is
  * data[offsets[i], offsets[i + 1]) and is decoded into the channels[i] (1 or 3) uint8 planes of H x W starting at plane
  * planes[i] of out (out_planes planes in all), bit-identical with libjpeg-turbo's default decode (cv2.imread): BGR for colour,
