@@ -14,7 +14,7 @@ from . import dp
 from .floss import BCELoss, floss
 from .models.model_SP import model_SP
 from .optim import FusedAdam
-from .data.STdatas import staged_batches
+from .data.STdatas import augmenting, staged_batches
 from .utils import (AverageMeter, cfg, change_key_names, computeAAEAUC, make_layers, owned_state_dict, plot_loss,
                     save_checkpoint)
 
@@ -47,7 +47,8 @@ class SP():
     def __init__(self, lr=1e-7, loss_save='loss_SP.png', save_name='best_fusion.pth.tar', save_path='save',
                  loss_function='f', num_epoch=10, batch_size=10, device='0', resume=1,
                  pretrained_spatial='save/04_spatial.pth.tar', pretrained_temporal='save/03_temporal.pth.tar',
-                 traindata=None, valdata=None):
+                 traindata=None, valdata=None, augment=None):
+        self.augment = augment               # hipops.AugSpec: trainSP's batches are augmented in the resident gather (None: not)
         self.lr, self.loss_save, self.save_name, self.save_path = lr, loss_save, save_name, save_path
         os.makedirs(save_path, exist_ok=True)
         self.loss_function, self.num_epoch, self.batch_size = loss_function, num_epoch, batch_size
@@ -120,19 +121,20 @@ class SP():
         end = time.time()
         self.optimizer.zero_grad()
         # batch k + 1 is copied (and normalised) on a copy stream while step k computes: data.STdatas.staged_batches
-        for i, (sample, (input_s, input_t, target)) in _progress(enumerate(staged_batches(self.STTrainLoader, self.device))):
-            output = self.model(input_s, input_t)
-            loss = self.criterion(output, target.view(output.size()))
-            loss.backward()
-            self.optimizer.step()
-            self.optimizer.zero_grad()
-            batch_time.update(time.time() - end)
-            losses.update(loss.item(), input_s.size(0))
-            end = time.time()
-            if (i + 1) % 1000 == 0:
-                print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
-                      'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(self.epochnow, i + 1, len(self.STTrainLoader) + 1,
-                                                                      batch_time=batch_time, loss=losses))
+        with augmenting(getattr(self.STTrainLoader, 'dataset', None), self.augment, self.epochnow):
+            for i, (sample, (input_s, input_t, target)) in _progress(enumerate(staged_batches(self.STTrainLoader, self.device))):
+                output = self.model(input_s, input_t)
+                loss = self.criterion(output, target.view(output.size()))
+                loss.backward()
+                self.optimizer.step()
+                self.optimizer.zero_grad()
+                batch_time.update(time.time() - end)
+                losses.update(loss.item(), input_s.size(0))
+                end = time.time()
+                if (i + 1) % 1000 == 0:
+                    print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
+                          'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(self.epochnow, i + 1, len(self.STTrainLoader) + 1,
+                                                                          batch_time=batch_time, loss=losses))
         self.optimizer.check_finite()        # raises if a step of the epoch met NaN / inf gradients (the kernel skipped those elements)
         return losses.avg
 

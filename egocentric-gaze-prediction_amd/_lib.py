@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # EGAZE_HIP_LIB: load another build of the same C-ABI (kernel A/B runs: csrc/build.sh -D... -o variant); default in-tree .so
@@ -124,6 +124,8 @@ SIGNATURES = {
     "egz_cat2_planes": (c_int, [P, P, P, c_int, c_long, S]),
     "egz_u8_normalize": (c_int, [P, P, c_long, c_long, c_int, P, P, S]),
     "egz_resident_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P, S]),
+    "egz_resident_gather_aug": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P,
+                                        c_uint64, c_uint64, c_uint64, c_int, c_float, c_float, P, P, S]),
     "egz_late_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, S]),
     "egz_lstm_pool_fetch": (c_int, [P, c_long, c_int, P, P, P, c_long, P, P, P, P, c_long, P, S]),
     "egz_crop_mean": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, S]),

@@ -100,6 +100,16 @@ def staged_batches(loader, device, stage=None):
         yield sample, staged
 
 
+def augmenting(dataset, spec, epoch):
+    """The context a training loop iterates in: ``dataset.augmenting(spec, epoch)`` when ``spec`` (a hipops.AugSpec) is set and
+    the dataset is a resident one, else a no-op -- the host path has no augmentation (the CLIs refuse the flag without
+    --gpu_resident)."""
+    import contextlib
+    if spec is not None and hasattr(dataset, 'augmenting'):
+        return dataset.augmenting(spec, epoch)
+    return contextlib.nullcontext()
+
+
 # ----------------------------------------------------------------------------- decode='gpu'
 # A sample holds its 22 files as bytes; the worker's collate (collate_gpu) joins a batch's streams into one pinned buffer,
 # stage_batch copies it in one H2D transfer and hipops.jpeg_decode decodes every stream into its plane of one uint8 batch

@@ -8,6 +8,7 @@ section 15 has the memory arithmetic.
 A sample of this dataset is its number; the collated batch carries the numbers and the dataset, and the two staging choke
 points (data.STdatas.stage_batch / to_raw_u8, streamtrain.stage_stream) turn it into tensors.  The DataLoader, its samplers and
 their RNG draws are those of the host dataset, so a seeded run visits the same samples in the same batches."""
+import contextlib
 import time
 import warnings
 
@@ -135,6 +136,7 @@ class ResidentSTDataset(STDataset):
         self.collate_fn = self._collate
         self.pool = self.table = None       # device tensors after fill()
         self._plan = None
+        self._augment = None                # (AugSpec, epoch) inside augmenting()
 
     # ------------------------------------------------------------------ plan (host only)
     def plan(self):
@@ -193,13 +195,38 @@ class ResidentSTDataset(STDataset):
         return {'index': index, 'fixsac': torch.FloatTensor([self.fixsac[index]]), 'imname': self.listTrainFiles[index]}
 
     def _collate(self, batch):
-        return {'resident': self, 'index': torch.LongTensor([s['index'] for s in batch]),
-                'fixsac': torch.stack([s['fixsac'] for s in batch]), 'imname': [s['imname'] for s in batch]}
+        out = {'resident': self, 'index': torch.LongTensor([s['index'] for s in batch]),
+               'fixsac': torch.stack([s['fixsac'] for s in batch]), 'imname': [s['imname'] for s in batch]}
+        if self._augment is not None:       # inside augmenting(): the batch is gathered through resident_gather_aug
+            out['augment'] = self._augment
+        return out
+
+    @contextlib.contextmanager
+    def augmenting(self, spec, epoch):
+        """While inside, every batch this dataset collates is stamped with ``(spec, epoch)`` (a hipops.AugSpec and the driver's
+        epoch number) and ``gather`` augments it on the device (hipops.resident_gather_aug); outside nothing is stamped.  The
+        stamp is put on at collation, and ``loader_workers`` is 0, so collation happens in the consuming process: the batch
+        that data.STdatas.staged_batches collates and stages one step ahead gets the stamp of the block its loop runs in.  A
+        training loop wraps its iteration in this and leaves it in a ``finally``; validation and the extraction passes run
+        outside and never see an augmented batch."""
+        from ..hipops import AugSpec
+        if not isinstance(spec, AugSpec):
+            raise ValueError(f"ResidentSTDataset.augmenting: spec must be a hipops.AugSpec, got {type(spec).__name__}")
+        before, self._augment = self._augment, (spec, int(epoch))
+        try:
+            yield self
+        finally:
+            self._augment = before
 
     def gather(self, sample, device, fields=None, raw=False, prepare=True):
         """The collated ``sample`` as device tensors: ``index`` crosses PCIe (non-blocking), one gather launch follows on the
-        current stream; its status word is left on ``sample`` for check_decode_status.  -> hipops.resident_gather's result."""
+        current stream; its status word is left on ``sample`` for check_decode_status.  A sample stamped by ``augmenting`` goes
+        through hipops.resident_gather_aug (and refuses ``raw``).  -> hipops.resident_gather's result."""
         from .. import hipops as H
+        stamp = sample.get('augment')
+        if stamp is not None and raw:       # the AT extraction reads raw bytes: it must never be augmented by accident
+            raise RuntimeError("ResidentSTDataset: a batch collated inside augmenting() was asked for as raw bytes "
+                               "(raw=True is the extraction path, which is never augmented)")
         if self.pool is None:
             raise RuntimeError("ResidentSTDataset: fill(device) has not run (the pool is not on the device)")
         if torch.device(device) != self.pool.device:
@@ -209,6 +236,9 @@ class ResidentSTDataset(STDataset):
         if missing:
             raise RuntimeError(f"ResidentSTDataset: field(s) {missing} were not in gpu_fields when the pool was filled")
         idx = sample['index'].to(self.pool.device, non_blocking=True)
+        if stamp is not None:
+            return H.resident_gather_aug(self.pool, self.table, idx, stamp[0], stamp[1], fields=fields, prepare=prepare,
+                                         status_to=sample)
         return H.resident_gather(self.pool, self.table, idx, fields=fields, raw=raw, prepare=prepare, status_to=sample)
 
 

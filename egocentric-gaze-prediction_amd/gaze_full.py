@@ -10,7 +10,8 @@ from torch.utils.data import DataLoader
 
 
 def build_parser():
-    p = argparse.ArgumentParser()
+    from .streamtrain import _CheckedParser, add_augment_flags
+    p = _CheckedParser()
     a = p.add_argument
     a('--lr_late', type=float, default=1e-4, required=False, help='lr for LF Adam')
     a('--lr', type=float, default=1e-7, required=False, help='lr for SP Adam')
@@ -64,6 +65,7 @@ def build_parser():
     a('--lstm_resident', action='store_true', default=argparse.SUPPRESS,
       help="AT stage: read the extracted LSTM vectors once and keep them in device memory (data.lstm_resident); every step of "
            "the LSTM training and validation fetches its input and target on the GPU.  Honours --gpu_resident_gb")
+    add_augment_flags(p)                  # the SP stage's training loop only: validation, AT and LF never see an augmented batch
     return p
 
 
@@ -152,6 +154,7 @@ def main(argv=None):
     from .LF import LF
     from .SP import SP
     from .data.STdatas import STDataset
+    from .streamtrain import augment_spec
     from . import dp
     if 'LOCAL_RANK' in os.environ and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         import datetime
@@ -183,7 +186,8 @@ def main(argv=None):
         sp = SP(lr=args.lr, loss_save=args.sp_save_img, save_name=args.save_sp, save_path=args.save_path,
                 loss_function=args.loss_function, num_epoch=args.num_epoch, batch_size=args.batch_size_sp,
                 device=args.device, resume=args.sp_resume, pretrained_spatial=args.pretrained_spatial,
-                pretrained_temporal=args.pretrained_temporal, traindata=STTrainData, valdata=STValData)
+                pretrained_temporal=args.pretrained_temporal, traindata=STTrainData, valdata=STValData,
+                augment=augment_spec(args))
         sp.train()
         args.pretrained_model = os.path.join(args.save_path, args.save_sp)
     # Under torch.distributed the AT stage's two extraction passes are sharded over the ranks, chunk by chunk, without changing

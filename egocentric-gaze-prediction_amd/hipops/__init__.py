@@ -133,9 +133,9 @@ from .lstm import (  # noqa: E402,F401
 )
 from .metrics import _GAUSS_W, _gauss_weights, aae_auc  # noqa: E402,F401
 from .dataprep import (  # noqa: E402,F401
-    RESIDENT_STATUS, _AREA_T, _NORM_CONST, _RESIDENT_FIELDS, _area_tables, area_table, bilinear_up,
+    AugSpec, RESIDENT_STATUS, _AREA_T, _NORM_CONST, _RESIDENT_FIELDS, _area_tables, area_table, bilinear_up,
     check_resident_status, crop_mean, gaze_gt_maps, late_gather, pixel_weighted_sum, resident_gather,
-    u8_center_of_mass, u8_normalize, weighted_minmax, window_mean,
+    resident_gather_aug, u8_center_of_mass, u8_normalize, weighted_minmax, window_mean,
 )
 from .jpeg import (  # noqa: E402,F401
     JPEG_ENCODE_STATUS, JPEG_STATUS, _SUBSAMPLING, _dev_table, _jpeg_encode_args, _jpeg_encode_scan, jpeg_decode,

@@ -1,6 +1,8 @@
-"""Dataset preparation and input pipeline: gaze maps, u8 normalise, the resident gathers (SP / AT and late fusion), AT glue."""
+"""Dataset preparation and input pipeline: gaze maps, u8 normalise, the resident gathers (SP / AT, with and without augmentation, and late fusion), AT glue."""
 from __future__ import annotations
 
+import dataclasses
+import math
 import sys
 from typing import Optional
 
@@ -203,6 +205,150 @@ def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, 
     else:
         _H.check_resident_status((host, done))
     return out_raw if raw else (image, flow, gt)
+
+
+# ----------------------------------------------------------------------------- augmentation in the gather
+RESIDENT_STATUS.update({
+    4: "an explicit augmentation row out of range (flip not 0 / 1, |dy| or |dx| above 32767, or a non-finite gain / bias)",
+    5: "a sample number outside the table and an explicit augmentation row out of range",
+    6: "a plane-table entry outside the pool and an explicit augmentation row out of range",
+    7: "a sample number outside the table, a plane-table entry outside the pool and an explicit augmentation row out of range"})
+
+
+@dataclasses.dataclass(frozen=True)
+class AugSpec:
+    """What resident_gather_aug draws per sample: ``flip`` the probability of a horizontal flip, ``shift`` the largest
+    translation in pixels (dy and dx uniform in -shift .. shift), ``contrast`` / ``brightness`` the amplitudes of the colour
+    frame's gain (1 +- contrast) and bias (+- brightness), ``seed`` the seed of the hash the draw comes from."""
+    flip: float = 0.0
+    shift: int = 0
+    contrast: float = 0.0
+    brightness: float = 0.0
+    seed: int = 0
+
+    def __post_init__(self):
+        for name, typ in (("flip", float), ("shift", int), ("contrast", float), ("brightness", float), ("seed", int)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int,) if typ is int else (int, float)):
+                raise ValueError(f"AugSpec: {name} = {v!r} is not {'an integer' if typ is int else 'a number'}")
+            object.__setattr__(self, name, typ(v))
+        if not 0.0 <= self.flip <= 1.0:
+            raise ValueError(f"AugSpec: flip = {self.flip} is not a probability in [0, 1]")
+        if not 0 <= self.shift <= 32767:
+            raise ValueError(f"AugSpec: shift = {self.shift} outside 0 .. 32767 pixels")
+        for name in ("contrast", "brightness"):
+            if not 0.0 <= getattr(self, name) < 1.0:
+                raise ValueError(f"AugSpec: {name} = {getattr(self, name)} outside [0, 1)")
+        if not 0 <= self.seed < 1 << 64:
+            raise ValueError(f"AugSpec: seed = {self.seed} outside 0 .. 2^64 - 1")
+
+    @property
+    def flip_thr(self) -> int:
+        """floor(flip * 2^32): a sample is flipped when the high half of its first hash word is below it."""
+        return int(math.floor(self.flip * 4294967296.0))
+
+    @classmethod
+    def parse(cls, text: str, seed: Optional[int] = None) -> "AugSpec":
+        """'flip=0.5,shift=16,contrast=0.2,brightness=0.1' (any subset, also 'seed=N'; a bare 'flip' means 0.5) -> AugSpec;
+        ``seed``, when given, replaces the text's."""
+        kw = {}
+        for item in str(text).split(","):
+            key, eq, val = (s.strip() for s in item.partition("="))
+            if key not in ("flip", "shift", "contrast", "brightness", "seed") or key in kw:
+                raise ValueError(f"AugSpec.parse: {item.strip()!r} in {text!r}: expected each of flip, shift, contrast, "
+                                 f"brightness, seed at most once, as name=value")
+            if not eq:
+                if key != "flip":
+                    raise ValueError(f"AugSpec.parse: {key!r} in {text!r} needs a value (only a bare 'flip' has one: 0.5)")
+                val = "0.5"
+            try:
+                kw[key] = int(val) if key in ("shift", "seed") else float(val)
+            except ValueError:
+                raise ValueError(f"AugSpec.parse: {key} = {val!r} in {text!r} is not a number") from None
+        if seed is not None:
+            kw["seed"] = seed
+        return cls(**kw)
+
+    def __str__(self):
+        return (f"flip={self.flip!r},shift={self.shift},contrast={self.contrast!r},brightness={self.brightness!r},"
+                f"seed={self.seed}")
+
+
+def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, spec: AugSpec, epoch: int,
+                        fields=('image', 'flow', 'gt'), raw: bool = False, prepare: bool = True,
+                        status_to: Optional[dict] = None, params: Optional[torch.Tensor] = None, want_params: bool = False):
+    """resident_gather with augmentation in the same launch (egz_resident_gather_aug): per sample a horizontal flip and an
+    integer translation applied alike to the colour frame, the flow planes (x-flow negated under a flip) and the ground truth,
+    and a gain / bias on the colour frame.  The parameters are drawn on the device from a hash of (spec.seed, epoch, sample
+    number) -- no host RNG is touched, and a sample's draw does not depend on its batch -- or taken from ``params``, an int32
+    (B, 5) tensor on the pool's device with rows flip, dy, dx, float bits of gain, float bits of bias.  Needs W % 4 == 0.
+    Everything else -- arguments, ``flow._egz_prepared``, the status word -- is resident_gather's; ``raw=True`` gives the bytes
+    after the geometric step.  -> resident_gather's result, or ``(result, parameters used (B, 5) int32)`` with
+    ``want_params``."""
+    from ..data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
+    if not isinstance(spec, AugSpec):
+        raise ValueError(f"resident_gather_aug: spec must be an AugSpec, got {type(spec).__name__}")
+    epoch = int(epoch)
+    if not 0 <= epoch < 1 << 64:
+        raise ValueError(f"resident_gather_aug: epoch = {epoch} outside 0 .. 2^64 - 1")
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
+            and pool.is_contiguous()):
+        raise ValueError("resident_gather_aug: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
+    dev = pool.device
+    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 22
+            and table.is_contiguous()):
+        raise ValueError("resident_gather_aug: table must be a contiguous int64 (N, 22) tensor on the pool's device")
+    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
+        raise ValueError("resident_gather_aug: idx must be a contiguous int64 (B,) tensor on the pool's device")
+    fields = tuple(fields)
+    if not fields or any(f not in _RESIDENT_FIELDS for f in fields):
+        raise ValueError(f"resident_gather_aug: fields {fields!r} must name some of 'image', 'flow', 'gt'")
+    P, H, W = pool.shape
+    B = idx.numel()
+    if params is not None and not (isinstance(params, torch.Tensor) and params.device == dev and params.dtype == torch.int32
+                                   and tuple(params.shape) == (B, 5) and params.is_contiguous()):
+        raise ValueError(f"resident_gather_aug: params must be a contiguous int32 ({B}, 5) tensor on the pool's device")
+    key = ('resident', dev.index or 0)
+    const = _NORM_CONST.get(key)
+    if const is None:
+        const = (torch.tensor(IMAGE_MEAN + FLOW_MEAN + (0.0,), dtype=torch.float32, device=dev),
+                 torch.tensor(IMAGE_STD + FLOW_STD + (1.0,), dtype=torch.float32, device=dev))
+        _NORM_CONST[key] = const
+    new = lambda C: torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    image = flow = gt = xin = am = out_raw = None
+    if raw:
+        out_raw = torch.empty((B, 24, H, W), dtype=torch.uint8, device=dev)
+    else:
+        image = new(3) if 'image' in fields else None
+        flow = new(20) if 'flow' in fields else None
+        gt = new(1) if 'gt' in fields else None
+        if flow is not None and prepare and _H.PRECISION == "split":
+            xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
+            am = _new_absmax(dev)
+    used = torch.empty((B, 5), dtype=torch.int32, device=dev) if want_params else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_resident_gather_aug(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
+                                      const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin), _p(am),
+                                      _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)), status.data_ptr(),
+                                      spec.seed, epoch, spec.flip_thr, spec.shift, spec.contrast, spec.brightness, _p(params),
+                                      _p(used), _stream()),
+          "egz_resident_gather_aug")
+    if xin is not None:
+        if _want_fwd_absmax():
+            xin._egz_absmax = am
+        ev = torch.cuda.Event()
+        ev.record()
+        flow._egz_prepared = (xin, flow._version, ev)
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_resident_status'] = (host, done)
+    else:
+        _H.check_resident_status((host, done))
+    out = out_raw if raw else (image, flow, gt)
+    return (out, used) if want_params else out
 
 
 def late_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, raw: bool = False,

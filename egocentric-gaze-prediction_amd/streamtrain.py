@@ -145,10 +145,13 @@ class GraphedStreamStep:
         self.step.close()
 
 
-def train_epoch(train_loader, model, criterion, optimizer, epoch, device, stream='spatial', hipgraph=False, every=5000):
+def train_epoch(train_loader, model, criterion, optimizer, epoch, device, stream='spatial', hipgraph=False, every=5000,
+                augment=None):
     """spatialstream.py:121-151.  Returns the epoch's mean loss (averaged over the ranks under torch.distributed).
     ``hipgraph``: full batches run as one captured step (GraphedStreamStep), a trailing partial batch eagerly; single process
-    only (the gradient all-reduce hooks are host code)."""
+    only (the gradient all-reduce hooks are host code).  ``augment``: a hipops.AugSpec; the batches of a resident dataset are
+    augmented in the gather under (its seed, ``epoch``, sample number).  The gather runs on the staging stream outside the
+    captured step, so seed and epoch passed by value never end up inside a graph."""
     spec = STREAMS[stream]
     device = torch.device(device)
     batch_time, losses = AverageMeter(), AverageMeter()
@@ -158,33 +161,34 @@ def train_epoch(train_loader, model, criterion, optimizer, epoch, device, stream
     encoder_grad = _optimised(model, optimizer)
     use_graph = hipgraph and dp.world_size() == 1 and device.type == 'cuda'
     stage = functools.partial(stage_stream, key=spec['key'], prepare=not use_graph)
-    from .data.STdatas import staged_batches
+    from .data.STdatas import augmenting, staged_batches
     graphed = None
-    try:
-        for i, (sample, (inp, target)) in _progress(enumerate(staged_batches(train_loader, device, stage))):
-            if use_graph and graphed is None:
-                graphed = GraphedStreamStep(model, criterion, optimizer, (inp, target), encoder_grad)
-            if graphed is not None and tuple(inp.shape) == graphed.shape:
-                loss, output = graphed(inp, target)
-            else:
-                if graphed is not None:
-                    optimizer.zero_grad()      # (a replay leaves its gradient in the buffers: the captured step zeroes first)
-                output = step_forward(model, inp, encoder_grad)
-                target = target.view(output.size())
-                loss = criterion(output, target)
-                loss.backward()
-                optimizer.step()
-                optimizer.zero_grad()
-            losses.update(loss.item(), inp.size(0))
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if (i + 1) % every == 0:
-                print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
-                      'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(epoch, i + 1, len(train_loader) + 1,
-                                                                      batch_time=batch_time, loss=losses))
-    finally:
-        if graphed is not None:        # leaves capturable mode, the host step count follows the device counter
-            graphed.close()
+    with augmenting(getattr(train_loader, 'dataset', None), augment, epoch):     # left on every way out
+        try:
+            for i, (sample, (inp, target)) in _progress(enumerate(staged_batches(train_loader, device, stage))):
+                if use_graph and graphed is None:
+                    graphed = GraphedStreamStep(model, criterion, optimizer, (inp, target), encoder_grad)
+                if graphed is not None and tuple(inp.shape) == graphed.shape:
+                    loss, output = graphed(inp, target)
+                else:
+                    if graphed is not None:
+                        optimizer.zero_grad()      # (a replay leaves its gradient in the buffers: the captured step zeroes first)
+                    output = step_forward(model, inp, encoder_grad)
+                    target = target.view(output.size())
+                    loss = criterion(output, target)
+                    loss.backward()
+                    optimizer.step()
+                    optimizer.zero_grad()
+                losses.update(loss.item(), inp.size(0))
+                batch_time.update(time.time() - end)
+                end = time.time()
+                if (i + 1) % every == 0:
+                    print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
+                          'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(epoch, i + 1, len(train_loader) + 1,
+                                                                          batch_time=batch_time, loss=losses))
+        finally:
+            if graphed is not None:        # leaves capturable mode, the host step count follows the device counter
+                graphed.close()
     if hasattr(optimizer, 'check_finite'):
         optimizer.check_finite()        # raises if a step of the epoch met NaN / inf gradients (the kernel skipped those elements)
     if dp.world_size() > 1:
@@ -237,7 +241,7 @@ def evaluate(val_loader, model, criterion, epoch, device, stream='spatial'):
 def build_parser(stream):
     """The reference's flags and defaults (spatialstream.py:15-30 / temporalstream.py:14-29), plus ``--hipgraph``."""
     spec = STREAMS[stream]
-    p = argparse.ArgumentParser()
+    p = _CheckedParser()
     p.add_argument('--lr', type=float, default=1e-7, required=False)
     p.add_argument('--loss_save', default=spec['loss_save'], required=False)
     p.add_argument('--save_name', default=spec['save_name'], required=False)
@@ -264,7 +268,44 @@ def build_parser(stream):
     p.add_argument('--gpu_resident_gb', type=float, default=argparse.SUPPRESS,
                    help='device memory the resident dataset may take, in GB, shared by the training and validation sets '
                         '(default: 0.8 x what is free)')
+    add_augment_flags(p)
     return p
+
+
+class _CheckedParser(argparse.ArgumentParser):
+    """An ArgumentParser that refuses ``--augment`` / ``--augment_seed`` without ``--gpu_resident``, and a spec that does not
+    parse, as it refuses any other bad command line."""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if (hasattr(ns, 'augment') or hasattr(ns, 'augment_seed')) and not getattr(ns, 'gpu_resident', False):
+            self.error("--augment / --augment_seed need --gpu_resident: augmentation happens in the gather over the resident "
+                       "pool, the host loading path has none")
+        if hasattr(ns, 'augment_seed') and not hasattr(ns, 'augment'):
+            self.error("--augment_seed without --augment")
+        if hasattr(ns, 'augment'):
+            try:
+                augment_spec(ns)
+            except ValueError as e:
+                self.error(f"--augment: {e}")
+        return ns, rest
+
+
+def add_augment_flags(parser):
+    """``--augment SPEC`` / ``--augment_seed N`` (absent from the namespace unless given); ``parser`` is a _CheckedParser."""
+    parser.add_argument('--augment', metavar='SPEC', default=argparse.SUPPRESS,
+                        help="augment the training batches in the resident gather: 'flip=0.5,shift=16,contrast=0.2,"
+                             "brightness=0.1' (any subset; a bare 'flip' means 0.5).  Needs --gpu_resident")
+    parser.add_argument('--augment_seed', type=int, metavar='N', default=argparse.SUPPRESS,
+                        help='seed of the augmentation draw (default 0); the draw depends on (seed, epoch, sample number) only')
+
+
+def augment_spec(args):
+    """The hipops.AugSpec of a parsed command line, None without ``--augment``."""
+    if not hasattr(args, 'augment'):
+        return None
+    from .hipops import AugSpec
+    return AugSpec.parse(args.augment, seed=getattr(args, 'augment_seed', None))
 
 
 def build_model(stream, resume=0, pretrained_model=None):
@@ -354,7 +395,8 @@ def main(stream, argv=None):
     for epoch in range(args.num_epoch):
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
-        train_loss.append(train_epoch(train_loader, model, criterion, optimizer, epoch, device, stream, args.hipgraph))
+        train_loss.append(train_epoch(train_loader, model, criterion, optimizer, epoch, device, stream, args.hipgraph,
+                                      augment=augment_spec(args)))
         loss1 = validate(val_loader, model, criterion, epoch, device, stream)
         val_loss.append(loss1)
         if dp.is_main():

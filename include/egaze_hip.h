@@ -482,6 +482,22 @@ int egz_u8_normalize(const unsigned char* src, float* dst, long n, long plane, i
 int egz_resident_gather(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H, int W,
                         const float* mean, const float* std, float* image, float* flow, float* gt, float* flow_nhwc32,
                         unsigned int* absmax, unsigned char* raw, int raw_fields, int* status, hipStream_t stream);
+/* egz_resident_gather with data augmentation in the same launch.  Per sample: a horizontal flip and an
+ * integer translation (dy, dx) applied alike to the colour frame, the flow planes and the ground truth -- out(y, x) =
+ * F(y - dy, x - dx), F the flipped frame; colour and flow replicate the edge, the ground truth is 0 outside the frame; an x-flow
+ * plane (table columns 1, 3, ..., 19) becomes 255 - byte under a flip -- and on the colour frame alone v = min(max(gain * (u8 /
+ * 255) + bias, 0), 1) before the normalisation, each operation rounded once.  raw carries the geometric step only.  The
+ * parameters are drawn on the device from a hash of (seed, epoch, idx[b]) -- flip with probability flip_thr / 2^32 (0 <= flip_thr
+ * <= 2^32), dy, dx in -max_shift .. max_shift (0 <= max_shift <= 32767), gain in 1 +- contrast, bias in +- brightness (both
+ * amplitudes in [0, 1)) -- unless params_in (device, (B, 5) int32 rows flip, dy, dx, float bits of gain, float bits of bias) is
+ * non-null: then its rows are used.  params_out (device, same layout, optional) receives the parameters used.  flip 0, dy = dx =
+ * 0, gain 1, bias 0 reproduce egz_resident_gather bit for bit.  W % 4 == 0 and H * W < 2^31.  *status: bits 0 and 1 as above;
+ * bit 2 = an explicit row with flip outside {0, 1}, |dy| or |dx| above 32767 or a non-finite gain / bias: the sample was skipped. */
+int egz_resident_gather_aug(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H, int W,
+                            const float* mean, const float* std, float* image, float* flow, float* gt, float* flow_nhwc32,
+                            unsigned int* absmax, unsigned char* raw, int raw_fields, int* status, unsigned long long seed,
+                            unsigned long long epoch, unsigned long long flip_thr, int max_shift, float contrast,
+                            float brightness, const int* params_in, int* params_out, hipStream_t stream);
 /* A late-fusion batch gathered from such a pool (data/late_resident.py, csrc/batch_gather.hip).  pool (P, H, W) uint8; table
  * (N, 3) int64 plane numbers per sample -- column 0 the SP prediction, 1 the AT map, 2 the ground truth; idx (B,) int64 sample
  * numbers.  Outputs, each optional (null: not produced, nothing written): fused (B,2,H,W) fp32, channel 0 the AT map and
