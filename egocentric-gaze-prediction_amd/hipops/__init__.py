@@ -133,7 +133,7 @@ from .lstm import (  # noqa: E402,F401
 )
 from .metrics import _GAUSS_W, _gauss_weights, aae_auc  # noqa: E402,F401
 from .dataprep import (  # noqa: E402,F401
-    AugSpec, RESIDENT_STATUS, _AREA_T, _NORM_CONST, _RESIDENT_FIELDS, _area_tables, area_table, bilinear_up,
+    AFFINE_STATUS, AugSpec, RESIDENT_STATUS, _AREA_T, _NORM_CONST, _RESIDENT_FIELDS, _area_tables, area_table, bilinear_up,
     check_resident_status, crop_mean, gaze_gt_maps, late_gather, pixel_weighted_sum, resident_gather,
     resident_gather_aug, u8_center_of_mass, u8_normalize, weighted_minmax, window_mean,
 )

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import dataclasses
 import math
+import struct
 import sys
 from typing import Optional
 
@@ -138,7 +139,8 @@ def check_resident_status(pending) -> None:
     ev.synchronize()
     st = int(host[0])
     if st:
-        raise RuntimeError(f"resident_gather: {RESIDENT_STATUS.get(st, st)}: the sample was skipped, its outputs are undefined")
+        what = RESIDENT_STATUS.get(st) or AFFINE_STATUS.get(st, st)
+        raise RuntimeError(f"resident_gather: {what}: the sample was skipped, its outputs are undefined")
 
 
 def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, fields=('image', 'flow', 'gt'),
@@ -215,19 +217,32 @@ RESIDENT_STATUS.update({
     7: "a sample number outside the table, a plane-table entry outside the pool and an explicit augmentation row out of range"})
 
 
+# Status values 8 .. 15: bit 3, an explicit row of the affine gather whose magnification or angle is out
+# of range, alone and with each combination of bits 0 .. 2.  A table of its own: RESIDENT_STATUS keeps the seven values of the
+# entry points without the affine step; check_resident_status reads both.
+_AFFINE_ROW = "an explicit augmentation row with a magnification outside [0.5, 1.5], an angle beyond 45 degrees or either non-finite"
+AFFINE_STATUS = {8: _AFFINE_ROW}
+AFFINE_STATUS.update({8 + st: f"{RESIDENT_STATUS[st]}, and {_AFFINE_ROW}" for st in range(1, 8)})
+
+
 @dataclasses.dataclass(frozen=True)
 class AugSpec:
     """What resident_gather_aug draws per sample: ``flip`` the probability of a horizontal flip, ``shift`` the largest
     translation in pixels (dy and dx uniform in -shift .. shift), ``contrast`` / ``brightness`` the amplitudes of the colour
-    frame's gain (1 +- contrast) and bias (+- brightness), ``seed`` the seed of the hash the draw comes from."""
+    frame's gain (1 +- contrast) and bias (+- brightness), ``seed`` the seed of the hash the draw comes from, ``scale`` the
+    amplitude of the magnification (1 +- scale, at most 0.5) and ``rotate`` that of the rotation about the frame's centre in
+    degrees (+- rotate, at most 45)."""
     flip: float = 0.0
     shift: int = 0
     contrast: float = 0.0
     brightness: float = 0.0
     seed: int = 0
+    scale: float = 0.0
+    rotate: float = 0.0
 
     def __post_init__(self):
-        for name, typ in (("flip", float), ("shift", int), ("contrast", float), ("brightness", float), ("seed", int)):
+        for name, typ in (("flip", float), ("shift", int), ("contrast", float), ("brightness", float), ("seed", int),
+                          ("scale", float), ("rotate", float)):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, (int,) if typ is int else (int, float)):
                 raise ValueError(f"AugSpec: {name} = {v!r} is not {'an integer' if typ is int else 'a number'}")
@@ -241,22 +256,36 @@ class AugSpec:
                 raise ValueError(f"AugSpec: {name} = {getattr(self, name)} outside [0, 1)")
         if not 0 <= self.seed < 1 << 64:
             raise ValueError(f"AugSpec: seed = {self.seed} outside 0 .. 2^64 - 1")
+        if not 0.0 <= self.scale <= 0.5:
+            raise ValueError(f"AugSpec: scale = {self.scale} outside [0, 0.5]")
+        if not 0.0 <= self.rotate <= 45.0:
+            raise ValueError(f"AugSpec: rotate = {self.rotate} outside [0, 45] degrees")
 
     @property
     def flip_thr(self) -> int:
         """floor(flip * 2^32): a sample is flipped when the high half of its first hash word is below it."""
         return int(math.floor(self.flip * 4294967296.0))
 
+    @property
+    def rotate_rad(self) -> float:
+        """The rotation amplitude in radians as the fp32 value the device draws with: rounded once from fp64."""
+        return struct.unpack("f", struct.pack("f", self.rotate * math.pi / 180.0))[0]
+
+    @property
+    def affine(self) -> bool:
+        """Whether the draw magnifies or rotates: then the gather is egz_resident_gather_affine's."""
+        return self.scale != 0.0 or self.rotate != 0.0
+
     @classmethod
     def parse(cls, text: str, seed: Optional[int] = None) -> "AugSpec":
-        """'flip=0.5,shift=16,contrast=0.2,brightness=0.1' (any subset, also 'seed=N'; a bare 'flip' means 0.5) -> AugSpec;
-        ``seed``, when given, replaces the text's."""
+        """'flip=0.5,shift=16,contrast=0.2,brightness=0.1,scale=0.15,rotate=10' (any subset, also 'seed=N'; a bare 'flip' means
+        0.5) -> AugSpec; ``seed``, when given, replaces the text's."""
         kw = {}
         for item in str(text).split(","):
             key, eq, val = (s.strip() for s in item.partition("="))
-            if key not in ("flip", "shift", "contrast", "brightness", "seed") or key in kw:
+            if key not in ("flip", "shift", "contrast", "brightness", "seed", "scale", "rotate") or key in kw:
                 raise ValueError(f"AugSpec.parse: {item.strip()!r} in {text!r}: expected each of flip, shift, contrast, "
-                                 f"brightness, seed at most once, as name=value")
+                                 f"brightness, seed, scale, rotate at most once, as name=value")
             if not eq:
                 if key != "flip":
                     raise ValueError(f"AugSpec.parse: {key!r} in {text!r} needs a value (only a bare 'flip' has one: 0.5)")
@@ -270,8 +299,12 @@ class AugSpec:
         return cls(**kw)
 
     def __str__(self):
-        return (f"flip={self.flip!r},shift={self.shift},contrast={self.contrast!r},brightness={self.brightness!r},"
+        text = (f"flip={self.flip!r},shift={self.shift},contrast={self.contrast!r},brightness={self.brightness!r},"
                 f"seed={self.seed}")
+        for name in ("scale", "rotate"):                  # printed only when in use: a spec without them prints as it always did
+            if getattr(self, name) != 0.0:
+                text += f",{name}={getattr(self, name)!r}"
+        return text
 
 
 def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, spec: AugSpec, epoch: int,
@@ -284,7 +317,12 @@ def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tens
     (B, 5) tensor on the pool's device with rows flip, dy, dx, float bits of gain, float bits of bias.  Needs W % 4 == 0.
     Everything else -- arguments, ``flow._egz_prepared``, the status word -- is resident_gather's; ``raw=True`` gives the bytes
     after the geometric step.  -> resident_gather's result, or ``(result, parameters used (B, 5) int32)`` with
-    ``want_params``."""
+    ``want_params``.
+
+    A spec with ``scale`` or ``rotate``, or ``params`` of (B, 7) rows -- the five, then float bits of the magnification g and
+    of the angle theta in radians -- goes through egz_resident_gather_affine: the picture is magnified
+    and turned about its centre, sampled bilinearly, and the flow vectors turn and scale with it; the parameters used are then
+    (B, 7) rows.  Without either the launch and its results are the ones described above."""
     from ..data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
     if not isinstance(spec, AugSpec):
         raise ValueError(f"resident_gather_aug: spec must be an AugSpec, got {type(spec).__name__}")
@@ -306,8 +344,12 @@ def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tens
     P, H, W = pool.shape
     B = idx.numel()
     if params is not None and not (isinstance(params, torch.Tensor) and params.device == dev and params.dtype == torch.int32
-                                   and tuple(params.shape) == (B, 5) and params.is_contiguous()):
-        raise ValueError(f"resident_gather_aug: params must be a contiguous int32 ({B}, 5) tensor on the pool's device")
+                                   and tuple(params.shape) in ((B, 5), (B, 7)) and params.is_contiguous()):
+        raise ValueError(f"resident_gather_aug: params must be a contiguous int32 ({B}, 5) tensor on the pool's device"
+                         f" (({B}, 7) with a magnification and an angle)")
+    affine = spec.affine or (params is not None and params.shape[1] == 7)
+    if affine and params is not None and params.shape[1] != 7:
+        raise ValueError(f"resident_gather_aug: a spec with scale / rotate takes params of ({B}, 7) rows, got ({B}, 5)")
     key = ('resident', dev.index or 0)
     const = _NORM_CONST.get(key)
     if const is None:
@@ -325,14 +367,22 @@ def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tens
         if flow is not None and prepare and _H.PRECISION == "split":
             xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
             am = _new_absmax(dev)
-    used = torch.empty((B, 5), dtype=torch.int32, device=dev) if want_params else None
+    used = torch.empty((B, 7 if affine else 5), dtype=torch.int32, device=dev) if want_params else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(LIB.egz_resident_gather_aug(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
-                                      const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin), _p(am),
-                                      _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)), status.data_ptr(),
-                                      spec.seed, epoch, spec.flip_thr, spec.shift, spec.contrast, spec.brightness, _p(params),
-                                      _p(used), _stream()),
-          "egz_resident_gather_aug")
+    if affine:
+        check(LIB.egz_resident_gather_affine(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
+                                             const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin),
+                                             _p(am), _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)),
+                                             status.data_ptr(), spec.seed, epoch, spec.flip_thr, spec.shift, spec.contrast,
+                                             spec.brightness, _p(params), _p(used), spec.scale, spec.rotate_rad, _stream()),
+              "egz_resident_gather_affine")
+    else:
+        check(LIB.egz_resident_gather_aug(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
+                                          const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin),
+                                          _p(am), _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)),
+                                          status.data_ptr(), spec.seed, epoch, spec.flip_thr, spec.shift, spec.contrast,
+                                          spec.brightness, _p(params), _p(used), _stream()),
+              "egz_resident_gather_aug")
     if xin is not None:
         if _want_fwd_absmax():
             xin._egz_absmax = am

@@ -295,7 +295,9 @@ def add_augment_flags(parser):
     """``--augment SPEC`` / ``--augment_seed N`` (absent from the namespace unless given); ``parser`` is a _CheckedParser."""
     parser.add_argument('--augment', metavar='SPEC', default=argparse.SUPPRESS,
                         help="augment the training batches in the resident gather: 'flip=0.5,shift=16,contrast=0.2,"
-                             "brightness=0.1' (any subset; a bare 'flip' means 0.5).  Needs --gpu_resident")
+                             "brightness=0.1,scale=0.15,rotate=10' (any subset; a bare 'flip' means 0.5; scale is the "
+                             "amplitude of a magnification 1 +- scale, at most 0.5, rotate that of a rotation in degrees, at "
+                             "most 45).  Needs --gpu_resident")
     parser.add_argument('--augment_seed', type=int, metavar='N', default=argparse.SUPPRESS,
                         help='seed of the augmentation draw (default 0); the draw depends on (seed, epoch, sample number) only')
 

@@ -498,6 +498,24 @@ int egz_resident_gather_aug(const unsigned char* pool, long P, const long* table
                             unsigned int* absmax, unsigned char* raw, int raw_fields, int* status, unsigned long long seed,
                             unsigned long long epoch, unsigned long long flip_thr, int max_shift, float contrast,
                             float brightness, const int* params_in, int* params_out, hipStream_t stream);
+/* egz_resident_gather_aug with a magnification g and a rotation theta about the frame's centre c = ((W - 1) / 2, (H - 1) / 2)
+ * in the same launch: p_out = c + d + g R(theta) (F(p_src) - c), F the flip and d = (dx, dy) the shift
+ * above; theta in radians, positive turning the picture from +x towards +y (y down).  Every output pixel takes its source
+ * coordinate in 1/256 pixel from a Q16 inverse matrix -- fp32 polynomial sine and cosine and a correctly rounded 1 / g, each
+ * operation rounded once, then integers only -- and the bilinear mix of the four neighbouring bytes of every plane: colour and
+ * flow replicate the edge, the ground truth is 0 outside the frame, and the vector of a flow pair (table columns 1 + 2 k, 2 +
+ * 2 k) about byte 127.5 is turned and scaled by the forward matrix and clamped to 0 .. 255.  The draw adds two words of the same
+ * hash: g in 1 +- scale (0 <= scale <= 0.5), theta in +- rotate_rad (0 <= rotate_rad <= float32(pi / 4)); the other five
+ * parameters of a (seed, epoch, sample) are those of egz_resident_gather_aug.  params_in / params_out are (B, 7) int32 on the
+ * device: flip, dy, dx, bits(gain), bits(bias), bits(g), bits(theta).  g = 1 and theta = 0 reproduce egz_resident_gather_aug bit
+ * for bit.  W % 4 == 0 and H * W < 2^31.  *status: bits 0 .. 2 as above; bit 3 = an explicit row with g outside [0.5, 1.5],
+ * |theta| above float32(pi / 4) or a non-finite g / theta: the sample was skipped. */
+int egz_resident_gather_affine(const unsigned char* pool, long P, const long* table, long N, const long* idx, int B, int H,
+                               int W, const float* mean, const float* std, float* image, float* flow, float* gt,
+                               float* flow_nhwc32, unsigned int* absmax, unsigned char* raw, int raw_fields, int* status,
+                               unsigned long long seed, unsigned long long epoch, unsigned long long flip_thr, int max_shift,
+                               float contrast, float brightness, const int* params_in, int* params_out, float scale,
+                               float rotate_rad, hipStream_t stream);
 /* A late-fusion batch gathered from such a pool (data/late_resident.py, csrc/batch_gather.hip).  pool (P, H, W) uint8; table
  * (N, 3) int64 plane numbers per sample -- column 0 the SP prediction, 1 the AT map, 2 the ground truth; idx (B,) int64 sample
  * numbers.  Outputs, each optional (null: not produced, nothing written): fused (B,2,H,W) fp32, channel 0 the AT map and
