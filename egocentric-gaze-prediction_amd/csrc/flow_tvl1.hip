@@ -20,7 +20,7 @@ namespace {
 
 constexpr int NT = 256;
 constexpr int MAX_R = 16;            // Gaussian tap radius
-constexpr int MAX_LEVELS = 16;
+constexpr int MAX_LEVELS = 16;       // of the pyramid, part of the definition: hipops.FLOW_MAX_LEVELS, tests/flow_ref.py MAX_LEVELS
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 

@@ -146,7 +146,7 @@ from .vis import (  # noqa: E402,F401
     jet_table_restated, linear_table, resize_linear_u8,
 )
 from .flow import (  # noqa: E402,F401
-    FLOW_FUSED, FLOW_PRESMOOTH_SIGMA, _FLOW_TAPS, _FLOW_WS, _flow_dev, _flow_hw, _flow_k, _flow_params, _flow_taps,
+    FLOW_FUSED, FLOW_MAX_LEVELS, FLOW_PRESMOOTH_SIGMA, _FLOW_TAPS, _FLOW_WS, _flow_dev, _flow_hw, _flow_k, _flow_params, _flow_taps,
     bgr_to_gray_u8, flow_gauss, flow_grad, flow_level_sizes, flow_pyramid_sigma, flow_resample, flow_to_u8,
     tvl1_flow, tvl1_iterate, tvl1_warp,
 )

@@ -16,6 +16,7 @@ _H = sys.modules[__package__]      # the package: switches and public functions 
 # csrc/flow_tvl1.hip; DESIGN.md "TV-L1 optical flow" is the definition, tests/flow_ref.py its numpy restatement.
 FLOW_PRESMOOTH_SIGMA = 0.8
 FLOW_FUSED = (1, 2, 3, 4, 6, 8)          # inner iterations per solver launch that are built (1: the streaming form)
+FLOW_MAX_LEVELS = 16                      # pyramid levels at most, whatever nscales asks for
 _FLOW_TAPS = {}
 _FLOW_WS = {}
 
@@ -39,9 +40,10 @@ def flow_pyramid_sigma(zfactor: float) -> float:
 
 
 def flow_level_sizes(H: int, W: int, nscales: int, zfactor: float):
-    """[(H, W), ...] of the pyramid, fine to coarse: nscales is clamped so that the coarsest level keeps 16 pixels per side."""
+    """[(H, W), ...] of the pyramid, fine to coarse: nscales is clamped so that the coarsest level keeps 16 pixels per side,
+    and to FLOW_MAX_LEVELS levels (MAX_LEVELS of the .hip file)."""
     sizes = [(int(H), int(W))]
-    while len(sizes) < nscales:
+    while len(sizes) < min(nscales, FLOW_MAX_LEVELS):
         h, w = int(sizes[-1][0] * zfactor + 0.5), int(sizes[-1][1] * zfactor + 0.5)
         if h < 16 or w < 16:
             break
@@ -123,7 +125,7 @@ def tvl1_flow(frames_gray_u8: torch.Tensor, *, tau: float = 0.25, lam: float = 0
 
     frames_gray_u8: (F, H, W) uint8 on the GPU, F >= 2, 16 <= H, W <= 2048.  -> (u1, u2), each (F - 1, H, W) float32:
     frame[i + 1](x + u[i]) ~ frame[i](x), u1 along x, u2 along y.  ``iterations`` inner iterations per warp, a fixed count;
-    nscales is clamped so that the coarsest level keeps 16 pixels per side.  fused: inner iterations per solver launch --
+    nscales is clamped so that the coarsest level keeps 16 pixels per side, and to 16 levels.  fused: inner iterations per solver launch --
     None = the measured default, 1 = one streaming launch per iteration, 2 / 3 / 4 / 6 / 8 = overlapped tiles; every choice gives the
     same bits.  The workspace is cached per (device, stream, F, H, W)."""
     what = "tvl1_flow"

@@ -8,6 +8,7 @@ import numpy as np
 
 DEFAULTS = dict(tau=0.25, lam=0.15, theta=0.3, nscales=5, zfactor=0.5, warps=5, iterations=30)
 PRESMOOTH_SIGMA = 0.8
+MAX_LEVELS = 16          # of the pyramid, whatever nscales asks for ("at most 16 levels")
 
 
 def gauss_weights(sigma, truncate=4.0):
@@ -23,9 +24,10 @@ def pyramid_sigma(zfactor):
 
 
 def level_sizes(H, W, nscales, zfactor):
-    """[(H, W), ...] from fine to coarse; nscales is clamped so that the coarsest level keeps 16 pixels per side."""
+    """[(H, W), ...] from fine to coarse; nscales is clamped so that the coarsest level keeps 16 pixels per side, and to
+    MAX_LEVELS levels."""
     sizes = [(int(H), int(W))]
-    while len(sizes) < nscales:
+    while len(sizes) < min(nscales, MAX_LEVELS):
         h, w = int(sizes[-1][0] * zfactor + 0.5), int(sizes[-1][1] * zfactor + 0.5)
         if h < 16 or w < 16:
             break
@@ -169,6 +171,7 @@ def iterate(state, consts, n, lam, theta, tau, dtype):
 
 
 def build_pyramid(frames_u8, nscales, zfactor, dtype):
+    """The presmoothed frames and their reductions, fine to coarse: the levels of level_sizes, so MAX_LEVELS at most."""
     pyr = [gauss_filter(frames_u8, PRESMOOTH_SIGMA, dtype)]
     for _ in level_sizes(*frames_u8.shape[-2:], nscales, zfactor)[1:]:
         pyr.append(pyramid_down(pyr[-1], zfactor, dtype))

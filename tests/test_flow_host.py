@@ -1,6 +1,7 @@
 """The definition of the TV-L1 flow (tests/flow_ref.py, the numpy restatement of DESIGN.md "TV-L1 optical flow") tested on its
-own, without a GPU: known translations of analytic textures, the quantiser, the grey rule, and the file naming and chunking of
-data/extract_flow.py with its device calls stubbed."""
+own, without a GPU: known translations of analytic textures, the pyramid's level sizes (the 16-pixel clamp and the 16-level cap,
+in both Python statements and in the library's workspace size), the quantiser, the grey rule, and the file naming and chunking
+of data/extract_flow.py with its device calls stubbed."""
 import os
 import sys
 
@@ -32,6 +33,44 @@ def test_level_sizes_clamp_to_16_pixels():
     assert R.level_sizes(33, 47, 5, 0.5) == [(33, 47), (17, 24)]
     assert R.level_sizes(16, 16, 5, 0.5) == [(16, 16)]
     assert R.level_sizes(256, 512, 3, 0.5) == [(256, 512), (128, 256), (64, 128)]
+
+
+def test_level_sizes_stop_at_16_levels_in_both_statements():
+    """The device carves its workspace for at most 16 levels (MAX_LEVELS of csrc/flow_tvl1.hip): the definition says so too."""
+    from egaze_amd import hipops as H
+    chain = [100, 90, 81, 73, 66, 59, 53, 48, 43, 39, 35, 32, 29, 26, 23, 21, 19, 17]     # 18 levels keep 16 pixels; 15 follows
+    for nscales in (15, 16, 17, 20, 1000):
+        want = [(v, v) for v in chain[:min(nscales, 16)]]
+        assert R.level_sizes(100, 100, nscales, 0.9) == H.flow_level_sizes(100, 100, nscales, 0.9) == want
+    assert R.MAX_LEVELS == H.FLOW_MAX_LEVELS == 16 == len(R.level_sizes(100, 100, 20, 0.9))
+    frames = np.zeros((2, 100, 100), np.uint8)
+    assert [p.shape[-2:] for p in R.build_pyramid(frames, 20, 0.9, np.float32)] == R.level_sizes(100, 100, 20, 0.9)
+    for args in ((224, 224, 5, 0.5), (33, 47, 5, 0.5), (16, 16, 5, 0.5), (256, 512, 3, 0.5), (273, 310, 5, 0.5), (65, 290, 5, 0.5),
+                 (64, 80, 10, 0.8), (96, 300, 5, 0.3), (2048, 2048, 20, 0.5)):
+        assert R.level_sizes(*args) == H.flow_level_sizes(*args), args
+    assert R.level_sizes(273, 310, 5, 0.5) == [(273, 310), (137, 155), (69, 78), (35, 39), (18, 20)]
+    assert len(R.level_sizes(64, 80, 10, 0.8)) == 7 and R.level_sizes(96, 300, 5, 0.3) == [(96, 300), (29, 90)]
+
+
+def test_workspace_size_counts_the_levels_of_the_definition():
+    """egz_tvl1_flow_ws_bytes is host code: its pyramid term is F floats per pixel of every level the definition lists, so the
+    library's own level_sizes agrees with the two Python ones, the 16-level cap included."""
+    from egaze_amd import _lib
+    for F, H, W, nscales, z in ((3, 100, 100, 20, 0.9), (3, 100, 100, 16, 0.9), (3, 100, 100, 15, 0.9), (3, 273, 310, 5, 0.5),
+                                (2, 65, 290, 5, 0.5), (3, 64, 80, 10, 0.8), (3, 96, 300, 5, 0.3), (35, 16, 272, 5, 0.5),
+                                (3, 64, 80, 1, 0.5), (3, 64, 80, 3, 0.5)):
+        pyr = sum(h * w for h, w in R.level_sizes(H, W, nscales, z))
+        assert _lib.LIB.egz_tvl1_flow_ws_bytes(F, H, W, nscales, z) == 4 * (F * H * W + F * pyr + 18 * (F - 1) * H * W)
+    assert _lib.LIB.egz_tvl1_flow_ws_bytes(3, 100, 100, 20, 0.9) == _lib.LIB.egz_tvl1_flow_ws_bytes(3, 100, 100, 16, 0.9)
+    assert _lib.LIB.egz_tvl1_flow_ws_bytes(3, 100, 100, 16, 0.9) > _lib.LIB.egz_tvl1_flow_ws_bytes(3, 100, 100, 15, 0.9)
+
+
+def test_pyramid_filter_radius_follows_zfactor():
+    """The radii the wide device tests rely on: 4 at zfactor 0.5, 2 at 0.8, 8 at 0.3; and the wrapper's sigma is the definition's."""
+    from egaze_amd import hipops as H
+    for z, radius in ((0.5, 4), (0.8, 2), (0.3, 8)):
+        assert H.flow_pyramid_sigma(z) == R.pyramid_sigma(z)
+        assert R.gauss_weights(R.pyramid_sigma(z))[1] == radius
 
 
 def test_quantiser_branches_and_ties():
