@@ -482,7 +482,31 @@ class AT():
         self.release_resident()                # nothing after the training reads the pools of ``resident=True``
         print('lstm training finished!')
 
-    def extract_late(self, st_loader, pred_folder='../new_pred/', feat_folder='../new_feat/', chunk=32, shard=None):
+    def _check_into(self, st_set, into):
+        """extract_late(into=...)'s preconditions, checked before any launch -> the ResidentSTDataset."""
+        from .data.late_resident import ResidentLateDataset
+        from .data.resident import ResidentSTDataset
+        who = "extract_late(into=)"
+        if not isinstance(st_set, ResidentSTDataset):
+            raise ValueError(f"{who}: st_loader.dataset must be a ResidentSTDataset (--gpu_resident), got "
+                             f"{type(st_set).__name__}: the frames are taken from its pool on the device")
+        if st_set.pool is None:
+            raise ValueError(f"{who}: the ResidentSTDataset has not been filled (fill(device))")
+        if st_set.pool.device != self.device:
+            raise ValueError(f"{who}: the ST pool is on {st_set.pool.device}, the AT stage runs on {self.device}")
+        missing = [f for f in ('image', 'flow', 'gt') if f not in (st_set._plan or ())]
+        if missing:
+            raise ValueError(f"{who}: field(s) {missing} were not in gpu_fields when the ST pool was filled")
+        if not (isinstance(into, ResidentLateDataset) and into._handover):
+            raise ValueError(f"{who}: into must be a ResidentLateDataset.from_st set")
+        if into.pool is None or into.pool.device != self.device:
+            raise ValueError(f"{who}: into.allocate({self.device}) has not run")
+        if len(into.st_index) and int(into.st_index.max()) >= len(st_set) or \
+                [st_set.listTrainFiles[i] for i in into.st_index.tolist()] != list(into.listFiles):
+            raise ValueError(f"{who}: into was not planned from this ST dataset")
+        return st_set
+
+    def extract_late(self, st_loader, pred_folder='../new_pred/', feat_folder='../new_feat/', chunk=32, shard=None, into=None):
         """pred = SP gaze map, feat = AT-weighted conv5_3 map, both written as uint8 PNGs (AT.py:199-253).
 
         The same sequential LSTM state as the reference's batch-1 loop, but the frames of the (batch-1) loader are gathered
@@ -503,17 +527,33 @@ class AT():
         EVERY rank runs the window's LSTM calls in chunk order (so the carried state is the same everywhere, bit for bit)
         and keeps the outputs of its own chunk, then weights, quantises and writes its own frames (stage B).  Each rank
         loads only its own frames, through a loader built over its indices of ``st_loader.dataset`` (a shuffling loader is
-        refused).  The files written are byte for byte those of ``shard=None``; ``shard=(0, 1)`` needs no process group."""
+        refused).  The files written are byte for byte those of ``shard=None``; ``shard=(0, 1)`` needs no process group.
+
+        ``into=late_set`` (a data.late_resident.ResidentLateDataset.from_st set of ``st_loader.dataset``, allocated on this
+        device): nothing is written to the folders; every chunk's two planes and its ground truth go straight into the
+        set's pool on the device (hipops.late_store) and the set is marked complete at the end.  ``st_loader.dataset`` must be
+        a filled ResidentSTDataset on this device with all three fields; its frames are gathered from the pool a chunk at
+        a time in dataset order (the loader itself is not iterated), the fixation flags are the dataset's host array, and
+        the only waits are for the status words, read once after the last chunk.  The forward of a chunk sees the bits and
+        runs the launches of the file path with the same ``chunk``, so the pool equals, byte for byte, what
+        ResidentLateDataset.fill decodes from that path's files -- for finite maps in [0, 1]; a NaN AT map (weighted_minmax of
+        a constant map) is stored as late_input's 0, which torch's float -> uint8 cast on the file path does not promise."""
         from . import dp
         cap = max(1, int(chunk))
         plan = None
+        if into is not None:
+            if shard is not None:
+                raise ValueError("extract_late: into= with shard= is not supported (a sharded extraction leaves every rank "
+                                 "with its own chunks only)")
+            st_set = self._check_into(getattr(st_loader, 'dataset', None), into)
         if shard is not None:
             rank_, world_ = dp.check_shard(shard)
             plan = dp.chunk_shards(len(getattr(st_loader, 'dataset', ())), cap, world_)
             st_loader = dp.owned_loader(st_loader, plan.indices(rank_))
         print('begin to extract files for training LF module ...')
-        os.makedirs(pred_folder, exist_ok=True)
-        os.makedirs(feat_folder, exist_ok=True)
+        if into is None:
+            os.makedirs(pred_folder, exist_ok=True)
+            os.makedirs(feat_folder, exist_ok=True)
         global features_blobs
         self.model.eval()
         self.lstm.eval()
@@ -563,15 +603,17 @@ class AT():
 
         dev_ = self.device
 
-        def stage_a(ch, n):
-            """Own frames up to the crop means: normalise, SP forward, uint8 quantisation, gaze point, crop means (n,512)."""
+        def stage_a(ch, n, staged=None):
+            """Own frames up to the crop means: normalise, SP forward, uint8 quantisation, gaze point, crop means (n,512).
+            ``staged``: the chunk's (image, flow, gt) already normalised on the device (the ``into=`` path's gather)."""
             t0 = time.perf_counter()
             if copy_stream is not None:
                 torch.cuda.current_stream().wait_stream(copy_stream)
-            input_s, input_t, target = stage_batch({k: ch.bufs[k][:n] for k in keys}, self.device)
+            input_s, input_t, target = staged or stage_batch({k: ch.bufs[k][:n] for k in keys}, self.device)
             t0 = mark("normalise", t0)
             del features_blobs[:]
             output = self.model(input_s, input_t)                     # (n,1,224,224)
+            ch.sp = output
             feature_s = features_blobs[0]                             # (n,512,14,14)
             t0 = mark("sp_forward", t0)
             quant = (255 * output).to(torch.uint8)                    # np.uint8(255 * x): truncation, on the device
@@ -679,6 +721,49 @@ class AT():
             ch.samples = []
             if prof is not None:
                 prof["finish_host"] = prof.get("finish_host", 0.0) + time.perf_counter() - t0
+
+        def store_chunks():
+            """The ``into=`` form: per chunk one gather launch over the ST pool, the forward and the LSTM call of launch(), and
+            one late_store launch; nothing is read back before the last chunk has been queued."""
+            N = len(st_set)
+            order = torch.arange(N, dtype=torch.int64, device=self.device)
+            rows = torch.full((N, 3), -1, dtype=torch.int64)          # a frame that `task` leaves out is forwarded, not stored
+            rows[into.st_index] = into.plane_table                    # (host rows: late_store checks them without a read-back)
+            pending, ch = [], _Chunk()
+            for k0 in _progress(range(0, N, cap)):
+                k1 = min(k0 + cap, N)
+                n, idx, status = k1 - k0, order[k0:k1], {}
+                t0 = time.perf_counter()
+                staged = H.resident_gather(st_set.pool, st_set.table, idx, fields=keys, status_to=status)
+                mark("gather", t0)
+                quant, feature_s, chn_weights = stage_a(ch, n, staged)
+                t0 = time.perf_counter()
+                at_idx, seq = chain(chn_weights, [int(f) for f in st_set.fixsac[k0:k1]])
+                if at_idx is not None:
+                    chn_weights = chn_weights.index_copy(0, at_idx, seq)
+                t0 = mark("lstm", t0)
+                feats = get_weighted_batch(chn_weights, feature_s)    # (n,14,14), as stage_b
+                H.late_store(ch.sp.reshape(n, *ch.sp.shape[-2:]), feats.contiguous(), into.pool, rows[k0:k1], gt_pool=st_set.pool,
+                             gt_src=st_set.table[k0:k1, 21].contiguous(), status_to=status)
+                mark("late_store", t0)
+                pending.append((k0, status))
+            for k0, status in pending:                                # the one place that waits for the device
+                H.check_resident_status(status['_resident_status'])
+                H.check_late_store_status(H.late_store_status(status['_late_store_status']),
+                                          who=f"extract_late(into=): frames {k0} .. {min(k0 + cap, N) - 1}")
+
+        if into is not None:
+            # The file path creates one iterator over st_loader, and creating it draws the loader's base seed from torch's
+            # global generator.  The same draw is made here (no sample is fetched), so that whatever is seeded after the
+            # extraction -- LF's initial weights, its shuffles -- is what it is after the file path.
+            if getattr(st_loader, 'num_workers', None) == 0:
+                iter(st_loader)
+            with torch.no_grad():
+                store_chunks()
+            H.lstm_persist_check()
+            into.mark_filled()
+            print('Finished extracting the LF planes into device memory!')
+            return
 
         ring, cur, prev = [_Chunk(), _Chunk()], 0, None
         kept = getattr(self, "_extract_buffers", None)               # device / pinned buffers survive across calls

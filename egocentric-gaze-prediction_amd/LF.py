@@ -109,11 +109,13 @@ class LF():
     def __init__(self, pretrained_model=None, save_path='save', late_save_img='loss_late.png',
                  save_name='best_late.pth.tar', device='0', late_pred_path='../new_pred', num_epoch=10,
                  late_feat_path='../new_feat', gt_path='../gtea_gts', val_name='Alireza', batch_size=32,
-                 loss_function='f', lr=1e-7, task=None, resident=False, decode='host', resident_gb=None):
+                 loss_function='f', lr=1e-7, task=None, resident=False, decode='host', resident_gb=None, datasets=None):
         """``resident``: both datasets are data.late_resident.ResidentLateDatasets, filled here (``decode``: how the one-time
         fill decodes; ``resident_gb``: the device memory both pools may take, default 0.8 x what is free); the loaders, their
         samplers and their RNG draws stay the file loader's, so a seeded run draws the same batches.  Under
-        torch.distributed every rank fills its own full pool."""
+        torch.distributed every rank fills its own full pool.  ``datasets=(train_set, val_set)``: two complete resident sets
+        on this device (ResidentLateDataset.from_st sets that AT.extract_late(into=...) has written) are used as they are: no
+        folder is listed, no file is read, and everything downstream is ``resident=True``'s."""
         self.model = late_fusion()
         self.device = torch.device('cuda:' + device)
         self.save_name, self.save_path = save_name, save_path
@@ -124,6 +126,47 @@ class LF():
             print('loaded pretrained late fusion model from ' + pretrained_model)
         self.model.to(self.device)
         self.batch_size, self.num_epoch, self.epochnow, self.late_save_img = batch_size, num_epoch, 0, late_save_img
+        if datasets is not None:
+            train_set, val_set = self._given_sets(datasets)
+        else:
+            train_set, val_set = self._listed_sets(late_pred_path, late_feat_path, gt_path, val_name, task, resident, decode,
+                                                   resident_gb)
+        collate = getattr(train_set, 'collate_fn', None)
+        # rank-sharded under torch.distributed (dp.RankShardSampler); the reference's loaders (LF.py:69-72) at world 1
+        self.train_sampler = dp.RankShardSampler(train_set, True, batch_size) if dp.world_size() > 1 else None
+        val_sampler = dp.RankShardSampler(val_set, False, batch_size, pad=False) if dp.world_size() > 1 else None
+        self.train_loader = DataLoader(dataset=train_set, batch_size=batch_size, shuffle=self.train_sampler is None,
+                                       sampler=self.train_sampler, num_workers=0, pin_memory=True, collate_fn=collate)
+        self.val_loader = DataLoader(dataset=val_set, batch_size=batch_size, shuffle=False, sampler=val_sampler,
+                                     num_workers=0, pin_memory=True, collate_fn=getattr(val_set, 'collate_fn', None))
+        self.criterion = (floss() if loss_function == 'f' else BCELoss()).to(self.device)
+        self.optimizer = FusedAdam(self.model.parameters(), lr=lr)
+        self.reducer = dp.attach(self.optimizer) if torch.distributed.is_initialized() else None
+        from . import hipops
+        print(hipops.precision_banner())
+
+    def _given_sets(self, datasets):
+        """``datasets=(train_set, val_set)``: two complete ResidentLateDatasets on this device, used as they are."""
+        from .data.late_resident import ResidentLateDataset
+        try:
+            train_set, val_set = datasets
+        except (TypeError, ValueError):
+            raise ValueError("LF: datasets must be (train_set, val_set)") from None
+        for name, ds in (("training", train_set), ("validation", val_set)):
+            if not isinstance(ds, ResidentLateDataset):
+                raise ValueError(f"LF: datasets: the {name} set must be a ResidentLateDataset, got {type(ds).__name__}")
+            if not ds.filled:
+                raise ValueError(f"LF: datasets: the {name} set is not complete (fill(), or AT.extract_late(into=...))")
+            if ds.pool.device != self.device:
+                raise ValueError(f"LF: datasets: the {name} set's pool is on {ds.pool.device}, LF runs on {self.device}")
+        print('num of training LF samples: %d' % len(train_set))
+        print('num of LF val samples: ', len(val_set))
+        assert(len(train_set) > 0)
+        self.stage = _stage_late_resident
+        return train_set, val_set
+
+    def _listed_sets(self, late_pred_path, late_feat_path, gt_path, val_name, task, resident, decode, resident_gb):
+        """The two datasets over the hand-over folders, as the reference lists them (LF.py:44-68)."""
         listGtFiles, listValGtFiles = _split(gt_path, val_name, task)
         print('num of training LF samples: %d' % len(listGtFiles))
         print('Loading SP predictions from /%s' % late_pred_path)
@@ -144,19 +187,7 @@ class LF():
         else:
             train_set = lateDataset(late_pred_path, gt_path, late_feat_path, listTrainFiles, listGtFiles, listTrainFeats)
             val_set = lateDataset(late_pred_path, gt_path, late_feat_path, listValFiles, listValGtFiles, listValFeats)
-        collate = getattr(train_set, 'collate_fn', None)
-        # rank-sharded under torch.distributed (dp.RankShardSampler); the reference's loaders (LF.py:69-72) at world 1
-        self.train_sampler = dp.RankShardSampler(train_set, True, batch_size) if dp.world_size() > 1 else None
-        val_sampler = dp.RankShardSampler(val_set, False, batch_size, pad=False) if dp.world_size() > 1 else None
-        self.train_loader = DataLoader(dataset=train_set, batch_size=batch_size, shuffle=self.train_sampler is None,
-                                       sampler=self.train_sampler, num_workers=0, pin_memory=True, collate_fn=collate)
-        self.val_loader = DataLoader(dataset=val_set, batch_size=batch_size, shuffle=False, sampler=val_sampler,
-                                     num_workers=0, pin_memory=True, collate_fn=getattr(val_set, 'collate_fn', None))
-        self.criterion = (floss() if loss_function == 'f' else BCELoss()).to(self.device)
-        self.optimizer = FusedAdam(self.model.parameters(), lr=lr)
-        self.reducer = dp.attach(self.optimizer) if torch.distributed.is_initialized() else None
-        from . import hipops
-        print(hipops.precision_banner())
+        return train_set, val_set
 
     def _run(self, loader, train, every):
         from .data.STdatas import staged_batches

@@ -141,6 +141,8 @@ SIGNATURES = {
     "egz_heatmap_overlay": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, P, P, P, P, P, P, S]),
     "egz_cell_argmax_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, S]),
     "egz_late_input": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, S]),
+    "egz_late_store": (c_int, [P, c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, c_long, P, P, c_long, P, P,
+                               S]),
     "egz_draw_ring": (c_int, [P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, c_int, S]),
     "egz_jpeg_decode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "egz_jpeg_decode": (c_int, [P, c_long, P, P, P, c_int, c_int, c_int, P, c_long, P, P, c_size_t, c_int, c_int, S]),

@@ -10,6 +10,10 @@
 // fp32 stores and 4-byte plane stores when H W is a multiple of 4 (else the same lanes go element by element); the h x w source of
 // the resize is a few hundred bytes per sample and stays in cache.
 //
+// egz_late_store: the training pipeline's form of the same hand-over (AT.extract_late(into=...)): the two planes of a chunk,
+// quantised and resized by the same code, go straight into the planes of a ResidentLateDataset pool that a (n, 3) table of
+// destinations names, and the ground-truth plane of each sample is copied there from the resident ST pool.  No fp32 output.
+//
 // egz_draw_ring: pixel (y, x) of image m takes the colour iff r_in^2 <= (y - cy)^2 + (x - cx)^2 <= r_out^2, in 64-bit integers;
 // a centre outside the image clips the ring.
 #include "egz_common.h"
@@ -61,6 +65,46 @@ struct LiTables {
     const short* yalpha;       // all null: the AT map already has H x W
 };
 
+// A resized fp32 map is judged where it is quantised, at its own resolution, once per sample (by the sample's first block): an
+// output pixel reads only the source elements its coefficients reach.
+__device__ __forceinline__ void li_judge(const void* __restrict__ at, long src, long hw, int& flags) {
+    for (long i = threadIdx.x; i < hw; i += LI_NT) (void)li_fetch<false>(at, src + i, flags);
+}
+
+// output pixels p0 .. p0 + n - 1 (n <= 4; the rest 0) of the h x w plane at element ``src`` resized to H x W
+template <bool AT_U8> __device__ __forceinline__ void li_resize4(const void* __restrict__ at, long src, long p0, int n, int W,
+                                                                 int h, int w, const LiTables& t, int* qa) {
+    int ignore = 0;                                 // (counted by li_judge)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        qa[e] = 0;
+        if (e < n) {
+            const long p = p0 + e;
+            const int y = (int)(p / W), x = (int)(p - (long)y * W);
+            const int sx = t.xofs[x], a0 = t.xalpha[2 * x], a1 = t.xalpha[2 * x + 1];
+            const int sy = t.yofs[y], b0 = t.yalpha[2 * y], b1 = t.yalpha[2 * y + 1];
+            const int x1 = min(sx + 1, w - 1);
+            const long r0 = src + (long)min(max(sy, 0), h - 1) * w, r1 = src + (long)min(max(sy + 1, 0), h - 1) * w;
+            qa[e] = linear_mix(li_fetch<AT_U8>(at, r0 + sx, ignore), li_fetch<AT_U8>(at, r0 + x1, ignore),
+                               li_fetch<AT_U8>(at, r1 + sx, ignore), li_fetch<AT_U8>(at, r1 + x1, ignore), a0, a1, b0,
+                               b1) & 0xff;                           // uchar(...) as OpenCV stores it
+        }
+    }
+}
+
+__device__ __forceinline__ unsigned int li_pack4(const int* q) {
+    return (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24);
+}
+
+// n quantised pixels (4 when VEC: one 4-byte store) into a uint8 plane
+template <bool VEC> __device__ __forceinline__ void li_put4(unsigned char* __restrict__ o, const int* q, int n) {
+    if constexpr (VEC) {
+        *reinterpret_cast<unsigned int*>(o) = li_pack4(q);
+    } else {
+        for (int e = 0; e < n; ++e) o[e] = (unsigned char)q[e];
+    }
+}
+
 // grid (ceil(H W / LI_TILE), B)
 template <bool SP_U8, bool AT_U8, bool VEC>
 __global__ __launch_bounds__(LI_NT) void late_input_kernel(const void* __restrict__ sp, const void* __restrict__ at, int H, int W,
@@ -70,41 +114,16 @@ __global__ __launch_bounds__(LI_NT) void late_input_kernel(const void* __restric
     const long HW = (long)H * W, hw = (long)h * w;
     const bool resize = t.xofs != nullptr;
     int flags = 0;
-    // A resized fp32 AT map is judged where it is quantised, at its own resolution, once per sample: an output pixel reads only
-    // the source elements its coefficients reach.
-    if (!AT_U8 && resize && blockIdx.x == 0) {
-        for (long i = threadIdx.x; i < hw; i += LI_NT) (void)li_fetch<false>(at, b * hw + i, flags);
-    }
+    if (!AT_U8 && resize && blockIdx.x == 0) li_judge(at, b * hw, hw, flags);
     const long p0 = (long)blockIdx.x * LI_TILE + 4 * threadIdx.x;
     if (p0 < HW) {
         const int n = (int)min(4L, HW - p0);
         int qs[4], qa[4];
         li_fetch4<SP_U8, VEC>(sp, b * HW + p0, n, qs, flags);
-        if (!resize) {
-            li_fetch4<AT_U8, VEC>(at, b * HW + p0, n, qa, flags);
-        } else {
-            int ignore = 0;                         // (counted above)
-            const long src = b * hw;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                qa[e] = 0;
-                if (e < n) {
-                    const long p = p0 + e;
-                    const int y = (int)(p / W), x = (int)(p - (long)y * W);
-                    const int sx = t.xofs[x], a0 = t.xalpha[2 * x], a1 = t.xalpha[2 * x + 1];
-                    const int sy = t.yofs[y], b0 = t.yalpha[2 * y], b1 = t.yalpha[2 * y + 1];
-                    const int x1 = min(sx + 1, w - 1);
-                    const long r0 = src + (long)min(max(sy, 0), h - 1) * w, r1 = src + (long)min(max(sy + 1, 0), h - 1) * w;
-                    qa[e] = linear_mix(li_fetch<AT_U8>(at, r0 + sx, ignore), li_fetch<AT_U8>(at, r0 + x1, ignore),
-                                       li_fetch<AT_U8>(at, r1 + sx, ignore), li_fetch<AT_U8>(at, r1 + x1, ignore), a0, a1, b0,
-                                       b1) & 0xff;                   // uchar(...) as OpenCV stores it
-                }
-            }
-        }
+        if (!resize) li_fetch4<AT_U8, VEC>(at, b * HW + p0, n, qa, flags);
+        else li_resize4<AT_U8>(at, b * hw, p0, n, W, h, w, t, qa);
         float* f_at = fused + ((long)b * 2 + 0) * HW + p0;
         float* f_sp = fused + ((long)b * 2 + 1) * HW + p0;
-        unsigned char* u_at = planes ? planes + ((long)b * 2 + 0) * HW + p0 : nullptr;
-        unsigned char* u_sp = planes ? planes + ((long)b * 2 + 1) * HW + p0 : nullptr;
         if constexpr (VEC) {
             f32x4 va, vs;
 #pragma unroll
@@ -114,21 +133,57 @@ __global__ __launch_bounds__(LI_NT) void late_input_kernel(const void* __restric
             }
             *reinterpret_cast<f32x4*>(f_at) = va;
             *reinterpret_cast<f32x4*>(f_sp) = vs;
-            if (planes) {
-                *reinterpret_cast<unsigned int*>(u_at) =
-                    (unsigned)qa[0] | ((unsigned)qa[1] << 8) | ((unsigned)qa[2] << 16) | ((unsigned)qa[3] << 24);
-                *reinterpret_cast<unsigned int*>(u_sp) =
-                    (unsigned)qs[0] | ((unsigned)qs[1] << 8) | ((unsigned)qs[2] << 16) | ((unsigned)qs[3] << 24);
-            }
         } else {
             for (int e = 0; e < n; ++e) {
                 f_at[e] = (float)qa[e] / 255.f;
                 f_sp[e] = (float)qs[e] / 255.f;
-                if (planes) {
-                    u_at[e] = (unsigned char)qa[e];
-                    u_sp[e] = (unsigned char)qs[e];
-                }
             }
+        }
+        if (planes) {
+            li_put4<VEC>(planes + ((long)b * 2 + 0) * HW + p0, qa, n);
+            li_put4<VEC>(planes + ((long)b * 2 + 1) * HW + p0, qs, n);
+        }
+    }
+    if (flags) atomicOr(status, flags);
+}
+
+// egz_late_store: the same two planes written where data/late_resident keeps them, and the ground-truth plane copied beside
+// them.  grid (ceil(H W / LI_TILE), n).  Every block of a sample reads the sample's four plane numbers and judges them alike: a
+// number outside its pool is never turned into an address, the sample writes nothing and bit 2 goes up (once, by the sample's
+// first block).  A destination of -1 skips its plane: the map behind it is neither read nor judged.
+template <bool SP_U8, bool AT_U8, bool VEC>
+__global__ __launch_bounds__(LI_NT) void late_store_kernel(const void* __restrict__ sp, const void* __restrict__ at, int H, int W,
+                                                           int h, int w, LiTables t, unsigned char* __restrict__ late_pool, long P,
+                                                           const long* __restrict__ dst, const unsigned char* __restrict__ gt_pool,
+                                                           long Q, const long* __restrict__ gt_src, int* __restrict__ status) {
+    const int b = blockIdx.y;
+    const long HW = (long)H * W, hw = (long)h * w;
+    const bool resize = t.xofs != nullptr;
+    const long d_sp = dst[3 * b], d_at = dst[3 * b + 1], d_gt = gt_pool ? dst[3 * b + 2] : -1;
+    const long s_gt = gt_pool ? gt_src[b] : 0;
+    if (d_sp < -1 || d_sp >= P || d_at < -1 || d_at >= P || d_gt < -1 || d_gt >= P || s_gt < 0 || (gt_pool && s_gt >= Q)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(status, 4);
+        return;
+    }
+    int flags = 0;
+    if (!AT_U8 && resize && d_at >= 0 && blockIdx.x == 0) li_judge(at, b * hw, hw, flags);
+    const long p0 = (long)blockIdx.x * LI_TILE + 4 * threadIdx.x;
+    if (p0 < HW) {
+        const int n = (int)min(4L, HW - p0);
+        int q[4];
+        if (d_sp >= 0) {
+            li_fetch4<SP_U8, VEC>(sp, b * HW + p0, n, q, flags);
+            li_put4<VEC>(late_pool + d_sp * HW + p0, q, n);
+        }
+        if (d_at >= 0) {
+            if (!resize) li_fetch4<AT_U8, VEC>(at, b * HW + p0, n, q, flags);
+            else li_resize4<AT_U8>(at, b * hw, p0, n, W, h, w, t, q);
+            li_put4<VEC>(late_pool + d_at * HW + p0, q, n);
+        }
+        if (d_gt >= 0) {
+            int ignore = 0;                         // (bytes: nothing to flag)
+            li_fetch4<true, VEC>(gt_pool, s_gt * HW + p0, n, q, ignore);
+            li_put4<VEC>(late_pool + d_gt * HW + p0, q, n);
         }
     }
     if (flags) atomicOr(status, flags);
@@ -181,6 +236,41 @@ EGZ_API int egz_late_input(const void* sp, int sp_u8, const void* at, int at_u8,
         },
         by_bool(sp_u8 != 0), by_bool(at_u8 != 0), by_bool(vec));
     EGZ_CHECK_LAUNCH("egz_late_input");
+    return 0;
+}
+
+// sp (n, H, W), at (n, h, w) and the tables as egz_late_input takes them.  late_pool (P, H, W) uint8; dst (n, 3) int64 on the
+// device: the planes of late_pool that take sample i's SP plane, AT plane and ground truth (-1: that plane is skipped).  gt_pool
+// (Q, H, W) uint8 with gt_src (n,) int64, both or neither: plane dst[i, 2] takes a copy of plane gt_src[i] of gt_pool; without
+// them the third column of dst is not read.  A row with a number outside [-1, P) in dst, or outside [0, Q) in gt_src, writes
+// nothing (bit 2 of status); the planes named within one call must be distinct (the caller's to check: the order of two
+// writers of one plane is not defined).  status: bits 0 and 1 as egz_late_input's, for the maps that were stored.
+EGZ_API int egz_late_store(const void* sp, int sp_u8, const void* at, int at_u8, int n, int H, int W, int h, int w,
+                           const int* xofs, const short* xalpha, const int* yofs, const short* yalpha, unsigned char* late_pool,
+                           long P, const long* dst, const unsigned char* gt_pool, long Q, const long* gt_src, int* status,
+                           hipStream_t st) {
+    EGZ_CHECK_ARG(sp && at && late_pool && dst && status, "egz_late_store: null pointer");
+    EGZ_CHECK_ARG(n > 0 && n <= 65535, "egz_late_store: n = %d outside 1 .. 65535", n);
+    EGZ_CHECK_ARG(H > 0 && W > 0 && h > 0 && w > 0, "egz_late_store: bad geometry (%d x %d -> %d x %d)", h, w, H, W);
+    EGZ_CHECK_ARG(P > 0, "egz_late_store: a pool of %ld planes", P);
+    EGZ_CHECK_ARG((gt_pool != nullptr) == (gt_src != nullptr), "egz_late_store: gt_pool and gt_src go together");
+    EGZ_CHECK_ARG(!gt_pool || Q > 0, "egz_late_store: a ground-truth pool of %ld planes", Q);
+    const bool tables = xofs && xalpha && yofs && yalpha;
+    EGZ_CHECK_ARG(tables || (!xofs && !xalpha && !yofs && !yalpha), "egz_late_store: the four resize tables go together");
+    EGZ_CHECK_ARG(tables || (h == H && w == W), "egz_late_store: %d x %d -> %d x %d needs the resize tables", h, w, H, W);
+    const long HW = (long)H * W;
+    // one 4-byte store per lane and plane needs every plane of both pools to start on a 4-byte boundary
+    const bool vec = HW % 4 == 0 && li_aligned(late_pool, 4) && li_aligned(gt_pool, 4) && li_aligned(sp, sp_u8 ? 4 : 16) &&
+                     (tables || li_aligned(at, at_u8 ? 4 : 16));
+    const LiTables t{tables ? xofs : nullptr, tables ? xalpha : nullptr, tables ? yofs : nullptr, tables ? yalpha : nullptr};
+    resolve(
+        [&](auto su8, auto au8, auto v) {
+            hipLaunchKernelGGL((late_store_kernel<decltype(su8)::value, decltype(au8)::value, decltype(v)::value>),
+                               dim3(egz_cdiv(HW, LI_TILE), n), dim3(LI_NT), 0, st, sp, at, H, W, h, w, t, late_pool, P, dst,
+                               gt_pool, Q, gt_src, status);
+        },
+        by_bool(sp_u8 != 0), by_bool(at_u8 != 0), by_bool(vec));
+    EGZ_CHECK_LAUNCH("egz_late_store");
     return 0;
 }
 

@@ -4,6 +4,9 @@ is decoded ONCE into a uint8 plane pool on the device, and a batch is one gather
 (hipops.late_gather: the gather, the three u8 / 255 normalisations and late_fusion's two-plane concatenation).  The loop then
 opens no file, decodes nothing and copies no pixel over PCIe.  DESIGN.md section 16 has the memory arithmetic.
 
+``ResidentLateDataset.from_st`` plans the same set from a resident ST dataset without any hand-over file; its pool is written on
+the device by ``AT.extract_late(into=...)`` (``gaze_full --late_handover``).
+
 As with data.resident, a sample of this dataset is its number: the collated batch carries the numbers and the dataset,
 LF's stage function turns it into tensors, and the DataLoader, its samplers and their RNG draws are the host dataset's."""
 import os
@@ -31,6 +34,7 @@ class ResidentLateDataset(lateDataset):
         self.collate_fn = self._collate
         self.pool = self.table = None       # device tensors after fill()
         self._plan = None
+        self._handover = self._complete = False     # from_st: the pool is written by AT.extract_late(into=...), not decoded
 
     def _files(self, index):
         return (os.path.join(self.imgPath_s, self.listFiles[index]), os.path.join(self.featPath, self.listFeat[index]),
@@ -62,12 +66,96 @@ class ResidentLateDataset(lateDataset):
         self._plan = True
         return self
 
+    # ------------------------------------------------------------------ planned from the ST dataset (no hand-over file)
+    @classmethod
+    def from_st(cls, st_dataset, task=None):
+        """The set ``LF`` would build from the files ``AT.extract_late`` writes for ``st_dataset`` (a ResidentSTDataset),
+        planned without touching a file: N = the samples that pass ``task``; ``plane_table`` is what plan() builds for N
+        distinct files per column (pred planes 0 .. N - 1, feat planes N .. 2N - 1, gt planes 2N .. 3N - 1); ``st_index`` (N,)
+        is the ST sample behind each row.  ``allocate(device)`` creates the zero-filled pool, ``AT.extract_late(into=...)``
+        writes it and marks the set complete; ``gather`` refuses until then.
+
+        The rows must be the rows ``LF`` lists: it sorts the written file names (the ``imname``s) and pairs them BY POSITION
+        with the sorted ground-truth names.  So the ``imname``s must be unique, in ``sorted()`` order, and sample i's own
+        ground-truth file the i-th of the dataset's sorted ground-truth list; anything else is refused, naming the first
+        offending sample."""
+        who = "ResidentLateDataset.from_st"
+        names, gts = list(st_dataset.listTrainFiles), list(st_dataset.listGtFiles)
+        if len(names) != len(gts):
+            raise ValueError(f"{who}: {len(names)} images but {len(gts)} ground-truth maps")
+        seen = {}
+        for i, name in enumerate(names):
+            if name in seen:
+                raise ValueError(f"{who}: sample {i} ({name}) has the name of sample {seen[name]}: both would be written to "
+                                 f"one hand-over file")
+            seen[name] = i
+        for i in range(1, len(names)):
+            if names[i - 1] > names[i]:
+                raise ValueError(f"{who}: sample {i} ({names[i]}) sorts before sample {i - 1} ({names[i - 1]}): LF lists the "
+                                 f"hand-over files in sorted order")
+        for i, (own, listed) in enumerate(zip(gts, sorted(gts))):
+            if own != listed:
+                raise ValueError(f"{who}: sample {i} ({names[i]}) has ground truth {own}, LF would pair it by position with "
+                                 f"{listed}")
+        keep = [i for i in range(len(names)) if task is None or task in names[i]]
+        if [gts[i] for i in keep] != [g for g in gts if task is None or task in g]:
+            bad = next(i for i in range(len(names)) if (task in names[i]) != (task in gts[i]))
+            raise ValueError(f"{who}: task {task!r} selects sample {bad}'s image ({names[bad]}) but not its ground truth "
+                             f"({gts[bad]}), or the reverse")
+        N = len(keep)
+        if N == 0:
+            raise RuntimeError(f"{who}: no samples (an empty dataset)")
+        if getattr(st_dataset, 'hw', None) is None:
+            st_dataset.plan()
+        kept = [names[i] for i in keep]
+        ds = cls(None, st_dataset.gtPath, None, kept, [gts[i] for i in keep], list(kept))
+        ds.files = None                      # nothing is decoded: extract_late writes the planes
+        ds.planes = COLS * N
+        ds.hw = tuple(st_dataset.hw)
+        ds.plane_table = torch.arange(COLS * N, dtype=torch.int64).view(COLS, N).t().contiguous()
+        ds.needed_bytes = ds.planes * ds.hw[0] * ds.hw[1] + ds.plane_table.numel() * 8
+        ds.st_index = torch.tensor(keep, dtype=torch.int64)
+        ds._plan = ds._handover = True
+        return ds
+
+    def allocate(self, device, budget_bytes=None):
+        """The zero-filled pool and the table of a from_st set on ``device``, under fill_planned's budget rule: a pool that
+        does not fit ``budget_bytes`` (None: 0.8 x the free device memory) raises before anything is allocated."""
+        if not self._handover:
+            raise RuntimeError("ResidentLateDataset.allocate: only a from_st set is allocated empty; fill() decodes the files")
+        device = torch.device(device)
+        if budget_bytes is None:
+            budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
+        if self.needed_bytes > budget_bytes:
+            raise RuntimeError(f"ResidentLateDataset.allocate: the late-fusion planes need {self.needed_bytes} bytes "
+                               f"({self.planes} planes of {self.hw[0]} x {self.hw[1]}), {budget_bytes} bytes are allowed: "
+                               f"run without --late_handover (there is no partial cache)")
+        self.pool = torch.zeros((self.planes,) + self.hw, dtype=torch.uint8, device=device)
+        self.table = self.plane_table.to(device)
+        self._complete = False
+        return self
+
+    def mark_filled(self):
+        """extract_late's last act: every row has been written, batches may be gathered."""
+        if self.pool is None:
+            raise RuntimeError("ResidentLateDataset.mark_filled: allocate(device) has not run")
+        self._complete = True
+        return self
+
+    @property
+    def filled(self):
+        """The pool is on the device and every plane of it has been written (by fill, or by the extraction of a from_st set)."""
+        return self.pool is not None and (not self._handover or self._complete)
+
     # ------------------------------------------------------------------ fill (decode once)
     def fill(self, device, budget_bytes=None, chunk=2048):
         """ResidentSTDataset.fill's rules: decodes every distinct file once, ``chunk`` files at a time, into its plane of the
         pool on ``device``; a pool that does not fit ``budget_bytes`` (None: 0.8 x the free device memory) raises before
         anything is allocated; corrupt data warns, an unsupported, unreadable or wrongly sized file raises, both naming the
         file."""
+        if self._handover:
+            raise RuntimeError("ResidentLateDataset.fill: a from_st set has no files to decode (allocate(), then "
+                               "AT.extract_late(into=...))")
         if not self._plan:
             self.plan()
         return fill_planned(self, device, budget_bytes, chunk, "ResidentLateDataset.fill", "--late_resident")
@@ -85,6 +173,8 @@ class ResidentLateDataset(lateDataset):
         from .. import hipops as H
         if self.pool is None:
             raise RuntimeError("ResidentLateDataset: fill(device) has not run (the pool is not on the device)")
+        if not self.filled:
+            raise RuntimeError("ResidentLateDataset: the pool is allocated but AT.extract_late(into=...) has not completed it")
         if torch.device(device) != self.pool.device:
             raise RuntimeError(f"ResidentLateDataset: the pool is on {self.pool.device}, the batch is asked for on {device}")
         idx = sample['index'].to(self.pool.device, non_blocking=True)

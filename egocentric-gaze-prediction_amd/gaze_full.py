@@ -11,7 +11,29 @@ from torch.utils.data import DataLoader
 
 def build_parser():
     from .streamtrain import _CheckedParser, add_augment_flags
-    p = _CheckedParser()
+
+    class _Parser(_CheckedParser):
+        """Also refuses ``--late_handover`` where it cannot work, as any other bad command line."""
+
+        def parse_known_args(self, args=None, namespace=None):
+            ns, rest = super().parse_known_args(args, namespace)
+            if getattr(ns, 'late_handover', False):
+                if not getattr(ns, 'gpu_resident', False):
+                    self.error("--late_handover needs --gpu_resident: the frames and the ground truth are taken from the "
+                               "resident pool on the device")
+                if not ns.extract_late:
+                    self.error("--late_handover needs --extract_late: the late-fusion planes exist only in the memory of the "
+                               "run that extracts them")
+                if not ns.train_late:
+                    self.error("--late_handover needs --train_late: the planes are not written anywhere, only this run's LF "
+                               "training can use them")
+                if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+                    self.error("--late_handover runs in one process: a sharded extraction leaves every rank with its own "
+                               "chunks only (WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
+                ns.late_resident = True
+            return ns, rest
+
+    p = _Parser()
     a = p.add_argument
     a('--lr_late', type=float, default=1e-4, required=False, help='lr for LF Adam')
     a('--lr', type=float, default=1e-7, required=False, help='lr for SP Adam')
@@ -65,6 +87,10 @@ def build_parser():
     a('--lstm_resident', action='store_true', default=argparse.SUPPRESS,
       help="AT stage: read the extracted LSTM vectors once and keep them in device memory (data.lstm_resident); every step of "
            "the LSTM training and validation fetches its input and target on the GPU.  Honours --gpu_resident_gb")
+    a('--late_handover', action='store_true', default=argparse.SUPPRESS,
+      help="with --gpu_resident --extract_late --train_late: the extraction writes the SP / AT planes and the ground truth "
+           "straight into the late-fusion pools on the device (no pred / feat file is written or read) and LF trains from "
+           "them.  Implies --late_resident; one process only.  Honours --gpu_resident_gb")
     add_augment_flags(p)                  # the SP stage's training loop only: validation, AT and LF never see an augmented batch
     return p
 
@@ -84,6 +110,28 @@ def _at_stage(args, STTrainData, STValData):
              resident_gb=getattr(args, 'gpu_resident_gb', None))
     if args.train_lstm:
         att.train()
+    if args.extract_late and getattr(args, 'late_handover', False):
+        # both late pools are planned and allocated, under what the ST pools left of --gpu_resident_gb, before the extraction
+        # starts: a pool that does not fit refuses here, not after the first pass
+        from .data.late_resident import ResidentLateDataset
+        late = [ResidentLateDataset.from_st(data, task=args.task) for data in (STTrainData, STValData)]
+        gb = getattr(args, 'gpu_resident_gb', None)
+        budget = None if gb is None else int(gb * 1e9) - sum(d.needed_bytes for d in (STTrainData, STValData))
+        if budget is None:
+            budget = int(0.8 * torch.cuda.mem_get_info(att.device)[0])
+        if sum(d.needed_bytes for d in late) > budget:
+            raise RuntimeError(f"--late_handover: the late-fusion planes need {sum(d.needed_bytes for d in late)} bytes, "
+                               f"{budget} bytes are left of the budget beside the resident dataset: run without "
+                               f"--late_handover (there is no partial cache)")
+        for d in late:
+            d.allocate(att.device, budget)
+            budget -= d.needed_bytes
+        if not args.train_lstm:
+            att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
+        for data, into in ((STValData, late[1]), (STTrainData, late[0])):
+            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=0,
+                                        collate_fn=data.collate_fn), into=into)
+        return tuple(late)
     if args.extract_late:
         if not args.train_lstm:
             att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
@@ -193,16 +241,18 @@ def main(argv=None):
     # Under torch.distributed the AT stage's two extraction passes are sharded over the ranks, chunk by chunk, without changing
     # a byte of what they write; only the LSTM training -- a batch-1, sequence-1 optimiser chain carried from sample to sample
     # across the whole dataset (AT.py:127-145) -- runs on rank 0 alone (_at_stage_sharded).  One rank: the calls as ever.
+    late_sets = None
     if dp.world_size() == 1:
-        _at_stage(args, STTrainData, STValData)
+        late_sets = _at_stage(args, STTrainData, STValData)
     else:
         _at_stage_sharded(args, STTrainData, STValData)
-    _lf_stage(args, (STTrainData, STValData))
+    _lf_stage(args, (STTrainData, STValData), late_sets)
 
 
-def _lf_stage(args, st_data=()):
+def _lf_stage(args, st_data=(), late_sets=None):
     """The LF stage.  ``--late_resident``: its two datasets are decoded once into device memory (data/late_resident.py), on the
-    GPU with ``--gpu_decode``, within ``--gpu_resident_gb``; the pools of ``--gpu_resident`` (``st_data``) are released first."""
+    GPU with ``--gpu_decode``, within ``--gpu_resident_gb``; the pools of ``--gpu_resident`` (``st_data``) are released first.
+    ``late_sets``: the (training, validation) sets ``--late_handover``'s extraction has written, handed to LF as they are."""
     from .LF import LF
     late_resident = getattr(args, 'late_resident', False)
     decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
@@ -215,7 +265,8 @@ def _lf_stage(args, st_data=()):
             save_name=args.save_late, device=args.device, late_pred_path=args.extract_late_pred_folder,
             num_epoch=args.num_epoch, late_feat_path=args.extract_late_feat_folder, gt_path=args.gtPath,
             val_name=args.val_name, batch_size=args.batch_size, loss_function=args.loss_function, lr=args.lr_late,
-            task=args.task, resident=late_resident, decode=decode, resident_gb=getattr(args, 'gpu_resident_gb', None))
+            task=args.task, resident=late_resident, decode=decode, resident_gb=getattr(args, 'gpu_resident_gb', None),
+            datasets=late_sets)
     if args.train_late:
         lf.train()
     else:

@@ -150,4 +150,7 @@ from .flow import (  # noqa: E402,F401
     bgr_to_gray_u8, flow_gauss, flow_grad, flow_level_sizes, flow_pyramid_sigma, flow_resample, flow_to_u8,
     tvl1_flow, tvl1_iterate, tvl1_warp,
 )
-from .handover import LATE_INPUT_STATUS, _map_dev, draw_ring, late_input, late_input_status  # noqa: E402,F401
+from .handover import (  # noqa: E402,F401
+    LATE_INPUT_STATUS, LATE_STORE_STATUS, _map_dev, check_late_store_status, draw_ring, late_input, late_input_status,
+    late_store, late_store_status,
+)

@@ -1,4 +1,5 @@
-"""The AT -> LF hand-over on the device (late_input) and the gaze marker of an overlay (draw_ring): predict.py's glue."""
+"""The AT -> LF hand-over on the device (late_input: predict.py's; late_store: AT.extract_late(into=...)'s, straight into a
+resident late-fusion pool) and the gaze marker of an overlay (draw_ring)."""
 from __future__ import annotations
 
 import sys
@@ -82,6 +83,107 @@ def late_input_status(pending) -> int:
     host, ev = pending
     ev.synchronize()
     return int(host[0])
+
+
+LATE_STORE_STATUS = {**LATE_INPUT_STATUS, 4: "a plane number outside its pool (that sample wrote nothing)"}
+
+
+def _pool_dev(t, name, what, dev, hw):
+    if not isinstance(t, torch.Tensor):
+        raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if not t.is_cuda or t.device != dev:
+        raise ValueError(f"{what}: {name} must be a HIP ('cuda') tensor on the maps' device {dev}, got {t.device}")
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[0] == 0:
+        raise ValueError(f"{what}: {name} must be a non-empty uint8 (P, H, W), got {t.dtype} {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
+    if tuple(t.shape[1:]) != hw:
+        raise ValueError(f"{what}: {name} holds planes of {tuple(t.shape[1:])}, sp has {hw}")
+    return t
+
+
+def late_store(sp: torch.Tensor, at: torch.Tensor, late_pool: torch.Tensor, dst: torch.Tensor,
+               gt_pool: Optional[torch.Tensor] = None, gt_src: Optional[torch.Tensor] = None, status_to: Optional[dict] = None):
+    """late_input's two planes of a chunk written straight into a late-fusion pool (data.late_resident), and the ground-truth
+    plane of every sample copied beside them, in one launch (egz_late_store).  No fp32 tensor is produced.
+
+    sp (n, H, W) and at (n, h, w): as late_input takes them.  late_pool: uint8 (P, H, W), contiguous, on the same GPU.  dst:
+    int64 (n, 3), the planes of late_pool that take the SP plane, the AT plane and the ground truth of each sample, in
+    ResidentLateDataset's column order; -1 skips a plane.  gt_pool: uint8 (Q, H, W) on the same GPU with gt_src: int64 (n,) on
+    that GPU, the plane of gt_pool each sample's ground truth is copied from; without them the third column is skipped.
+    A plane named twice in ``dst`` is refused (two writers of one plane have no defined order).  ``dst`` may be a host tensor:
+    it is checked there and uploaded from pinned memory without waiting for the device; a device ``dst`` is read back for the
+    check (a wait).  A number outside [-1, P) in ``dst`` or outside [0, Q) in ``gt_src`` is never dereferenced: that sample
+    writes nothing and bit 2 of the status word goes up; bits 0 / 1 are late_input's, for the maps that were stored.  The word
+    is read here (a wait; bits 0 / 1 warn, bit 2 raises), or, with ``status_to`` (a dict), left there as ``(pinned host word,
+    event)`` under '_late_store_status' for late_store_status.  -> late_pool."""
+    what = "late_store"
+    _map_dev(sp, "sp", what)
+    _map_dev(at, "at", what)
+    if sp.device != at.device:
+        raise ValueError(f"{what}: sp and at must be on one device ({sp.device} vs {at.device})")
+    if sp.shape[0] != at.shape[0]:
+        raise ValueError(f"{what}: {sp.shape[0]} SP maps but {at.shape[0]} AT maps")
+    n, Hh, Ww = (int(v) for v in sp.shape)
+    h, w = int(at.shape[1]), int(at.shape[2])
+    if n > 65535:
+        raise ValueError(f"{what}: {n} samples in one launch (65535 at most)")
+    dev = sp.device
+    _pool_dev(late_pool, "late_pool", what, dev, (Hh, Ww))
+    if (gt_pool is None) != (gt_src is None):
+        raise ValueError(f"{what}: gt_pool and gt_src go together")
+    if gt_pool is not None:
+        _pool_dev(gt_pool, "gt_pool", what, dev, (Hh, Ww))
+        if not (isinstance(gt_src, torch.Tensor) and gt_src.device == dev and gt_src.dtype == torch.int64
+                and tuple(gt_src.shape) == (n,) and gt_src.is_contiguous()):
+            raise ValueError(f"{what}: gt_src must be a contiguous int64 ({n},) tensor on {dev}")
+        lo, hi = late_pool.data_ptr(), late_pool.data_ptr() + late_pool.numel()
+        if gt_pool.data_ptr() < hi and lo < gt_pool.data_ptr() + gt_pool.numel():
+            raise ValueError(f"{what}: gt_pool overlaps late_pool")
+    if not (isinstance(dst, torch.Tensor) and dst.dtype == torch.int64 and tuple(dst.shape) == (n, 3)
+            and dst.is_contiguous() and (dst.device == dev or dst.device.type == 'cpu')):
+        raise ValueError(f"{what}: dst must be a contiguous int64 ({n}, 3) tensor on {dev} or on the host")
+    named = (dst if gt_pool is not None else dst[:, :2]).cpu().numpy().ravel()      # (a device dst: a wait)
+    named = named[named != -1]
+    if len(set(named.tolist())) != named.size:
+        seen = set()
+        twice = next(int(v) for v in named.tolist() if v in seen or seen.add(v))
+        raise ValueError(f"{what}: dst names plane {twice} twice in one call")
+    if dst.device.type == 'cpu':
+        pinned = torch.empty((n, 3), dtype=torch.int64, pin_memory=True)
+        pinned.copy_(dst)
+        dst = pinned.to(dev, non_blocking=True)
+    tabs = (None,) * 4 if (h, w) == (Hh, Ww) else _H._linear_tables(dev, (h, w), (Hh, Ww), what)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_late_store(sp.data_ptr(), int(sp.dtype == torch.uint8), at.data_ptr(), int(at.dtype == torch.uint8), n, Hh, Ww,
+                             h, w, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]), late_pool.data_ptr(),
+                             late_pool.shape[0], dst.data_ptr(), _p(gt_pool), 0 if gt_pool is None else gt_pool.shape[0],
+                             _p(gt_src), status.data_ptr(), _stream()), "egz_late_store")
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_late_store_status'] = (host, done)
+    else:
+        check_late_store_status(_H.late_store_status((host, done)), stacklevel=3)
+    return late_pool
+
+
+def late_store_status(pending) -> int:
+    """Waits for the late_store launch that ``pending = (host status word, event)`` belongs to -> its status word
+    (LATE_STORE_STATUS names the bits)."""
+    return late_input_status(pending)
+
+
+def check_late_store_status(st: int, who: str = "late_store", stacklevel: int = 2):
+    """The rule for a late_store status word: bit 2 (a plane number outside its pool: samples were skipped) raises, bits 0 / 1
+    (defined values were stored) warn as late_input does."""
+    if st & 4:
+        raise RuntimeError(f"{who}: {LATE_STORE_STATUS[4]}")
+    if st:
+        import warnings
+        warnings.warn(f"{who}: {LATE_STORE_STATUS.get(st, st)}", RuntimeWarning, stacklevel=stacklevel)
 
 
 def draw_ring(images: torch.Tensor, centers: torch.Tensor, r_in: int, r_out: int, colour=(255, 255, 255)) -> torch.Tensor:

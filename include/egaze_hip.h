@@ -427,11 +427,20 @@ int egz_cell_argmax_u8(const unsigned char* gt, int N, int H, int W, int cell, i
  * fused (B, 2, H, W) fp32: channel 0 the AT plane, channel 1 the SP plane, every value (float)u8 / 255.f -- bit-identical
  * with egz_late_gather of the same planes; planes (B, 2, H, W) uint8, optional (null: not written), the same two planes.
  * fused stays below 4 GiB.  No allocation, no synchronisation.
+ * late_store: the same two planes of n samples, quantised and resized by the same code, written into planes of late_pool
+ * (P, H, W) uint8: dst (n, 3) int64 on the device names the planes that take sample i's SP plane, AT plane and ground truth;
+ * -1 skips a plane (its map is then neither read nor flagged).  gt_pool (Q, H, W) uint8 and gt_src (n,) int64 go together:
+ * plane dst[i, 2] takes a copy of plane gt_src[i] of gt_pool; both null: the third column of dst is not read.  A row with a
+ * number outside [-1, P) in dst or outside [0, Q) in gt_src is never dereferenced, writes none of its planes and raises bit 2
+ * of *status; bits 0 and 1 as late_input's.  The planes named in one call must be distinct.  No fp32 output.
  * draw_ring: images (M, H, W, 3) uint8 in place; pixel (y, x) of image m takes (c0, c1, c2) iff
  * r_in^2 <= (y - centers[2m])^2 + (x - centers[2m + 1])^2 <= r_out^2 (integers); centres may lie outside the image. */
 int egz_late_input(const void* sp, int sp_u8, const void* at, int at_u8, int B, int H, int W, int h, int w, const int* xofs,
                    const short* xalpha, const int* yofs, const short* yalpha, float* fused, unsigned char* planes, int* status,
                    hipStream_t stream);
+int egz_late_store(const void* sp, int sp_u8, const void* at, int at_u8, int n, int H, int W, int h, int w, const int* xofs,
+                   const short* xalpha, const int* yofs, const short* yalpha, unsigned char* late_pool, long P, const long* dst,
+                   const unsigned char* gt_pool, long Q, const long* gt_src, int* status, hipStream_t stream);
 int egz_draw_ring(unsigned char* images, int M, int H, int W, const int* centers, int r_in, int r_out, int c0, int c1, int c2,
                   hipStream_t stream);
 
