@@ -285,21 +285,43 @@ class AT():
     def __init__(self, pretrained_model=None, pretrained_lstm=None, extract_lstm=False, crop_size=3,
                  num_epoch_lstm=30, lstm_save_img='loss_lstm.png', save_path='save', save_name='best_lstm.pth.tar',
                  device='0', lstm_data_path='../512w', traindata=None, valdata=None, task=None, align=False,
-                 shard=None, resident=False, resident_gb=None):
+                 shard=None, resident=False, resident_gb=None, lstm_handover=False, lstm_handover_chunk=1):
         """``shard=(rank, world)``: with ``extract_lstm`` every rank of the default process group extracts its share of the
         LSTM training data (extractLSTMw.extractw), then all meet at a barrier so that each lists the complete folders.
         ``resident``: both LSTM datasets are data.lstm_resident.ResidentLSTMDatasets, filled here on the device (``resident_gb``:
         the device memory both pools may take, default 0.8 x what is free); trainLSTM / testLSTM then fetch every step on the
-        GPU (_epoch_resident) and compute what they compute from the files, bit for bit."""
+        GPU (_epoch_resident) and compute what they compute from the files, bit for bit.
+        ``lstm_handover``: with ``extract_lstm`` and resident ST datasets (data.resident.ResidentSTDataset, filled), no
+        ``shard`` and no ``align``: both LSTM datasets are planned from the ST datasets (ResidentLSTMDataset.from_st),
+        allocated under what the ST pools left of ``resident_gb``, written on the device by the extraction
+        (extractLSTMw.extractw(into=...), ``lstm_handover_chunk`` frames per forward; 1 is the file path's schedule, bit for
+        bit) and used as they are: no folder under ``lstm_data_path`` is written, listed or read."""
         if pretrained_model is None:
             raise generalException('AT module have to use pretrained SP module.')
+        handover_sets = None
+        if lstm_handover:
+            handover_sets = self._plan_lstm_handover(extract_lstm, traindata, valdata, shard, align, task)
         self.device = torch.device('cuda:' + device)
         self.lstm = lstmnet().to(self.device)
         if pretrained_lstm is not None:
             self.reload_LSTM(pretrained_lstm)
         self.criterion_lstm = MSELoss.apply
         self.optimizer_lstm = FusedAdam(self.lstm.parameters(), lr=1e-4)
-        if extract_lstm:
+        if handover_sets is not None:
+            from .extractLSTMw import extract_LSTM_training_data
+            budget = int(0.8 * torch.cuda.mem_get_info(self.device)[0]) if resident_gb is None else \
+                int(resident_gb * 1e9) - sum(d.needed_bytes for d in (traindata, valdata))
+            if sum(d.needed_bytes for d in handover_sets) > budget:
+                raise RuntimeError(f"lstm_handover: the LSTM vectors need {sum(d.needed_bytes for d in handover_sets)} bytes, "
+                                   f"{budget} bytes are left of the budget beside the resident dataset: raise "
+                                   f"--gpu_resident_gb or run without --lstm_handover")
+            for d in handover_sets:             # both pools before the extraction starts: a pool that does not fit refuses here
+                d.allocate(self.device, budget)
+                budget -= d.needed_bytes
+            extract_LSTM_training_data(save_path=None, trained_model=pretrained_model, device=device, crop_size=crop_size,
+                                       traindata=traindata, valdata=valdata, align=align, into=handover_sets,
+                                       chunk=lstm_handover_chunk)
+        elif extract_lstm:
             from .extractLSTMw import extract_LSTM_training_data
             extract_LSTM_training_data(save_path=lstm_data_path, trained_model=pretrained_model, device=device,
                                        crop_size=crop_size, traindata=traindata, valdata=valdata, align=align, shard=shard)
@@ -315,6 +337,10 @@ class AT():
         self.model.load_state_dict(merged, strict=False)
         self.model.to(self.device)
         self.model._modules.get(hook_name).register_forward_hook(hook_feature)
+        if handover_sets is not None:          # the datasets are the sets the extraction has just written
+            self.lstmTrainLoader = DataLoader(dataset=handover_sets[0], batch_size=1, shuffle=False, num_workers=0)
+            self.lstmValLoader = DataLoader(dataset=handover_sets[1], batch_size=1, shuffle=False, num_workers=0)
+            return
         from .data.LSTMdatas import lstmDataset
         if resident:                           # the vectors live on the device; every step fetches there (data/lstm_resident.py)
             from .data.lstm_resident import ResidentLSTMDataset as lstmDataset
@@ -327,6 +353,25 @@ class AT():
                 loader.dataset.fill(self.device, resident_gb)
                 if resident_gb is not None:    # one budget for both pools
                     resident_gb -= loader.dataset.needed_bytes / 1e9
+
+    @staticmethod
+    def _plan_lstm_handover(extract_lstm, traindata, valdata, shard, align, task):
+        """``lstm_handover``'s preconditions, then the two planned sets (nothing is allocated, nothing launched)."""
+        from .data.lstm_resident import ResidentLSTMDataset
+        from .data.resident import ResidentSTDataset
+        if not extract_lstm:
+            raise ValueError("AT(lstm_handover=True) needs extract_lstm: the vectors exist only in the memory of the run "
+                             "that extracts them")
+        if shard is not None:
+            raise ValueError("AT(lstm_handover=True) runs in one process: a sharded extraction leaves every rank with its "
+                             "own vectors only")
+        if align:
+            raise ValueError("AT(lstm_handover=True) does not take align: the aligned window is built on the host")
+        for data in (traindata, valdata):
+            if not isinstance(data, ResidentSTDataset) or data.pool is None:
+                raise ValueError(f"AT(lstm_handover=True) needs filled ResidentSTDatasets (--gpu_resident), got "
+                                 f"{type(data).__name__}: the frames and the ground truth are taken from the pool on the device")
+        return tuple(ResidentLSTMDataset.from_st(data, task=task) for data in (traindata, valdata))
 
     def release_resident(self):
         """Frees the pools of ``resident=True``; the loaders go on reading the files."""

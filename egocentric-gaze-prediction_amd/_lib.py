@@ -130,6 +130,7 @@ SIGNATURES = {
                                            c_uint64, c_uint64, c_uint64, c_int, c_float, c_float, P, P, c_float, c_float, S]),
     "egz_late_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, S]),
     "egz_lstm_pool_fetch": (c_int, [P, c_long, c_int, P, P, P, c_long, P, P, P, P, c_long, P, S]),
+    "egz_lstm_store": (c_int, [P, c_int, c_int, c_int, c_int, P, c_long, P, c_int, c_int, P, c_long, P, P, P, S]),
     "egz_crop_mean": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, S]),
     "egz_window_mean": (c_int, [P, P, P, c_int, c_int, c_int, c_int, S]),
     "egz_pixel_weighted_sum": (c_int, [P, P, P, c_int, c_int, c_int, S]),

@@ -7,6 +7,7 @@
 //                        extractLSTMw.py:81-90): size x size window of the 14 x 14 map around gaze_point // 16.
 //   egz_weighted_minmax  AT.get_weighted (AT.py:58-66): channel-weighted sum of the map, min-max normalised.
 #include "egz_common.h"
+#include "window_mean.h"
 
 namespace {
 
@@ -47,11 +48,7 @@ __global__ void window_mean_kernel(const float* __restrict__ feat, const int* __
     const long idx = blockIdx.x * (long)blockDim.x + threadIdx.x;
     if (idx >= (long)B * C) return;
     const int b = (int)(idx / C), c = (int)(idx % C);
-    const int y0 = win[4 * b], y1 = win[4 * b + 1], x0 = win[4 * b + 2], x1 = win[4 * b + 3];
-    float s = 0.f;
-    for (int y = y0; y < y1; ++y)
-        for (int x = x0; x < x1; ++x) s += feat[(((long)b * H + y) * W + x) * C + c];
-    out[idx] = s / (float)((y1 - y0) * (x1 - x0));
+    out[idx] = egz_window_mean_at(feat, b, H, W, C, c, win[4 * b], win[4 * b + 1], win[4 * b + 2], win[4 * b + 3]);
 }
 
 // one thread per (b, c): out[b][c] = sum_p wmap[b][p] * feat[b][p][c]  (a linear functional of the map, e.g. the mean of a

@@ -5,7 +5,10 @@ device).  The loop then unpickles no file and copies no vector over PCIe.  DESIG
 
 Unlike data.resident / data.late_resident a sample of this dataset is NOT its number: ``__getitem__`` is lstmDataset's, so the
 dataset is also the file set -- what AT iterates before ``fill()``, after ``release()`` and wherever the fused single-step path
-is off."""
+is off.
+
+``ResidentLSTMDataset.from_st`` plans the same set from a resident ST dataset without any ``fix_*.pth.tar`` file; its pool is
+written on the device by ``extractLSTMw.extractw(into=...)`` (``gaze_full --lstm_handover``)."""
 import os
 
 import numpy as np
@@ -14,6 +17,7 @@ import torch
 from .LSTMdatas import deferred_steps, lstmDataset
 
 FILL_THREADS = 16                           # file reads of fill() in flight at most
+VECTOR_WIDTH = 512                          # channels of conv5_3: the length of an extracted vector (a from_st set has no file to ask)
 
 
 def lstm_plan(listFiles):
@@ -37,10 +41,93 @@ class ResidentLSTMDataset(lstmDataset):
         self.plan_host = lstm_plan(self.listFiles)
         self.n_steps = len(self.plan_host[0])
         self.needed_bytes = None            # known once the first file gave the vector length
+        self._handover = self._complete = False     # from_st: the pool is written by extractw(into=...), not read from files
+
+    # ------------------------------------------------------------------ planned from the ST dataset (no vector file)
+    @classmethod
+    def from_st(cls, st_dataset, task=None):
+        """The set ``lstmDataset(folder, task)`` would list after ``extractLSTMw.extractw`` had written its files for
+        ``st_dataset`` (an STDataset: ``fixsac``, ``listTrainFiles``), planned without looking at a folder.  The extracted
+        frames are the second frames of the fixations (a one-frame fixation raises the file path's RuntimeError here, before
+        anything is allocated); frame ``imname`` is file ``'fix_' + imname[:-4] + '.pth.tar'``; ``task`` keeps the names that
+        contain it; ``listFiles`` is the sorted names, and the row of a frame is its name's position there -- whatever the
+        order of the dataset.  Two frames with one name are refused (the file path would keep the later one only).
+        Sets ``plan_host`` = lstm_plan(listFiles), ``n_steps``, ``st_index`` (F,) int64, the ST sample behind each row, and
+        ``needed_bytes`` = F x 512 x 4 + 9 n_steps.  ``allocate(device)`` creates the zero-filled pool, ``extractw(into=...)``
+        writes it and marks the set complete; ``filled`` is False until then."""
+        from ..extractLSTMw import fixation_second_frames
+        who = "ResidentLSTMDataset.from_st"
+        names, flags = list(st_dataset.listTrainFiles), list(st_dataset.fixsac)
+        if len(flags) < len(names):
+            raise ValueError(f"{who}: {len(names)} frames but {len(flags)} fixation flags")
+        rows, seen = [], {}
+        for i in fixation_second_frames(flags[:len(names)]):
+            name = 'fix_' + names[i][:-4] + '.pth.tar'
+            if name in seen:
+                raise ValueError(f"{who}: sample {i} ({names[i]}) has the name of sample {seen[name]}: both would be written "
+                                 f"to {name}")
+            seen[name] = i
+            if task is None or task in name:
+                rows.append((name, i))
+        rows.sort()
+        ds = cls.__new__(cls)
+        ds.Path = None                          # no folder: the vectors exist in device memory only
+        ds.listFiles = [name for name, _ in rows]
+        ds.pool = ds.plan = None
+        ds.plan_host = lstm_plan(ds.listFiles)
+        ds.n_steps = len(ds.plan_host[0])
+        ds.width = VECTOR_WIDTH
+        ds.st_index = torch.tensor([i for _, i in rows], dtype=torch.int64)
+        ds.needed_bytes = len(rows) * ds.width * 4 + 9 * ds.n_steps
+        ds._handover, ds._complete = True, False
+        return ds
+
+    def allocate(self, device, budget_bytes=None):
+        """The zero-filled (F, 512) pool and the plan of a from_st set on ``device``, under fill's budget rule: a set that does
+        not fit ``budget_bytes`` (None: 0.8 x the free device memory) raises before anything is allocated."""
+        if not self._handover:
+            raise RuntimeError("ResidentLSTMDataset.allocate: only a from_st set is allocated empty; fill() reads the files")
+        self.release()
+        device = torch.device(device)
+        F = len(self.listFiles)
+        if F == 0:
+            raise RuntimeError("ResidentLSTMDataset.allocate: no vectors (no second fixation frame passes the task filter)")
+        if budget_bytes is None:
+            budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
+        if self.needed_bytes > budget_bytes:
+            raise RuntimeError(f"ResidentLSTMDataset.allocate: {F} vectors of {self.width} need {self.needed_bytes} bytes, "
+                               f"{budget_bytes} bytes are allowed: raise --gpu_resident_gb or run without --lstm_handover")
+        self.pool = torch.zeros((F, self.width), dtype=torch.float32, device=device)
+        self.plan = tuple(torch.from_numpy(a).to(device) for a in self.plan_host)
+        return self
+
+    def mark_filled(self):
+        """extractw's last act: every row has been written, the steps may be fetched."""
+        if self.pool is None:
+            raise RuntimeError("ResidentLSTMDataset.mark_filled: allocate(device) has not run")
+        self._complete = True
+        return self
 
     @property
     def filled(self):
-        return self.pool is not None
+        """The pool is on the device and every row of it has been written (by fill, or by the extraction of a from_st set)."""
+        return self.pool is not None and (not self._handover or self._complete)
+
+    def __getitem__(self, index):
+        """lstmDataset's sample.  A from_st set has no files: it serves the same dict from its pool rows (a read-back per
+        sample; only AT's paths beside the resident loop come here), and raises once the pool is gone."""
+        if not self._handover:
+            return super().__getitem__(index)
+        if not self.filled:
+            raise RuntimeError("ResidentLSTMDataset: the vectors of an in-memory hand-over (from_st, --lstm_handover) exist in "
+                               "device memory only, and the pool " +
+                               ("is not there (released, or never allocated)" if self.pool is None
+                                else "has not been completed by extractw(into=...)"))
+        if not 0 <= index < len(self):
+            raise IndexError(index)
+        a, b = self.listFiles[index], self.listFiles[index + 1]
+        pair = self.pool[index:index + 2].cpu()
+        return {'input': pair[0].clone(), 'gt': pair[1].clone(), 'same': b[:-14] == a[:-14]}
 
     def _read(self, name, want=None):
         v = torch.load(os.path.join(self.Path, name), map_location='cpu')
@@ -59,6 +146,9 @@ class ResidentLSTMDataset(lstmDataset):
         bytes, else RuntimeError before anything is allocated.  A file that is not float32, or not of the first file's length,
         raises ValueError naming it; the pool is None after either."""
         from concurrent.futures import ThreadPoolExecutor
+        if self._handover:
+            raise RuntimeError("ResidentLSTMDataset.fill: a from_st set has no files to read (allocate(), then "
+                               "extractLSTMw.extractw(into=...))")
         self.release()
         device = torch.device(device)
         F = len(self.listFiles)
@@ -84,5 +174,6 @@ class ResidentLSTMDataset(lstmDataset):
         return self
 
     def release(self):
-        """Drops the pool and the plan: the dataset is the file set again."""
+        """Drops the pool and the plan: the dataset is the file set again (a from_st set has none: its samples are gone)."""
         self.pool = self.plan = None
+        self._complete = False

@@ -77,8 +77,18 @@ def channel_weight(feat, gt, crop_size, align):
         from . import hipops as H
         from .functions import to_nhwc
         return H.window_mean(to_nhwc(feat), win).squeeze(0)
-    crop = crop_feature_var(feat, maxind, crop_size).contiguous()
-    return crop.view(crop.size(0), crop.size(1), -1).mean(2).squeeze(0)
+    return sequential_mean(crop_feature_var(feat, maxind, crop_size)).squeeze(0)
+
+
+def sequential_mean(crop):
+    """(B,C,h,w) window -> (B,C) spatial mean with egz_window_mean's arithmetic: the cells added one after the other in (y, x)
+    order in fp32, then one divide by their number.  torch's ``mean`` adds in several partial sums from 16 elements on, which
+    differs in the last bits; with this order host tensors and device tensors give channel_weight the same bits."""
+    flat = crop.reshape(crop.size(0), crop.size(1), -1)
+    s = torch.zeros_like(flat[:, :, 0])
+    for k in range(flat.size(2)):
+        s = s + flat[:, :, k]
+    return s / flat.size(2)
 
 
 class _SecondFrame:
@@ -122,14 +132,102 @@ def _shard_loader(loader, shard):
     return dp.owned_loader(loader, fixation_second_frames(flags)[rank_::world_])
 
 
-def extractw(loader, model, savepath, crop_size=3, device='0', align=False, shard=None):
+def _check_into(st_set, into, dev):
+    """extractw(into=...)'s preconditions, checked before any launch."""
+    from .data.lstm_resident import ResidentLSTMDataset
+    from .data.resident import ResidentSTDataset
+    who = "extractw(into=)"
+    if not isinstance(st_set, ResidentSTDataset):
+        raise ValueError(f"{who}: loader.dataset must be a ResidentSTDataset (--gpu_resident), got {type(st_set).__name__}: "
+                         f"the frames and the ground truth are taken from its pool on the device")
+    if st_set.pool is None:
+        raise ValueError(f"{who}: the ResidentSTDataset has not been filled (fill(device))")
+    if st_set.pool.device != dev:
+        raise ValueError(f"{who}: the ST pool is on {st_set.pool.device}, the extraction runs on {dev}")
+    missing = [f for f in ('image', 'gt') if f not in (st_set._plan or ())]
+    if missing:
+        raise ValueError(f"{who}: field(s) {missing} were not in gpu_fields when the ST pool was filled")
+    if not (isinstance(into, ResidentLSTMDataset) and into._handover):
+        raise ValueError(f"{who}: into must be a ResidentLSTMDataset.from_st set")
+    if into.pool is None or into.pool.device != dev:
+        raise ValueError(f"{who}: into.allocate({dev}) has not run")
+    index = into.st_index.tolist()
+    if (index and max(index) >= len(st_set)) or \
+            ['fix_' + st_set.listTrainFiles[i][:-4] + '.pth.tar' for i in index] != list(into.listFiles):
+        raise ValueError(f"{who}: into was not planned from this ST dataset")
+
+
+def _extract_into(loader, model, crop_size, dev, into, chunk):
+    """The ``into=`` form of extractw: the set's frames in dataset order, ``chunk`` at a time -- one gather launch over the ST
+    pool (the image alone), one encoder forward, one lstm_store launch that reads the ground truth where it lies in the pool
+    and writes the vectors into their rows.  Nothing is read back before the last chunk has been queued."""
+    from . import hipops as H
+    from .functions import to_nhwc
+    st_set = loader.dataset
+    rows_of = {i: r for r, i in enumerate(into.st_index.tolist())}
+    frames = sorted(rows_of)                                      # dataset order; a frame `task` filters out is not forwarded
+    index = torch.tensor(frames, dtype=torch.int64)
+    rows = torch.tensor([rows_of[i] for i in frames], dtype=torch.int64)      # (host rows: lstm_store checks them without a read-back)
+    index_dev = index.to(dev)
+    gt_src = st_set.table[:, 21].index_select(0, index_dev).contiguous()
+    pending = []
+    with torch.no_grad():
+        for k0 in range(0, len(frames), chunk):
+            k1, status = min(k0 + chunk, len(frames)), {}
+            image = H.resident_gather(st_set.pool, st_set.table, index_dev[k0:k1], fields=('image',), status_to=status)[0]
+            feat = model(image)                                   # (n,512,14,14)
+            H.lstm_store(to_nhwc(feat), st_set.pool, gt_src[k0:k1], into.pool, rows[k0:k1], crop_size, status_to=status)
+            pending.append((k0, k1, status))
+    # The one place that waits for the device, once: every status word was copied to pinned memory on this stream, in order, so
+    # when the last launch's word has landed all of them have.
+    if pending:
+        H.lstm_store_status(pending[-1][2]['_lstm_store_status'])
+    for k0, k1, status in pending:
+        if int(status['_resident_status'][0][0]):
+            H.check_resident_status(status['_resident_status'])
+        H.check_lstm_store_status(int(status['_lstm_store_status'][0][0]), who=f"extractw(into=): vectors {k0} .. {k1 - 1}")
+    into.mark_filled()
+
+
+def extractw(loader, model, savepath=None, crop_size=3, device='0', align=False, shard=None, into=None, chunk=1):
     """``shard=(rank, world)``: this rank extracts every ``world``-th of the frames a one-rank run extracts and loads no
     others (frames are independent and forwarded at batch 1, so its files are the one-rank run's bit for bit); no
-    collective, and file names are per frame, so ranks never collide."""
+    collective, and file names are per frame, so ranks never collide.
+
+    ``into=lstm_set`` (a data.lstm_resident.ResidentLSTMDataset.from_st set of ``loader.dataset``, allocated on this device):
+    no file is written and ``savepath`` is not looked at; every vector goes straight into its row of the set's pool
+    (hipops.lstm_store) and the set is marked complete at the end.  ``loader.dataset`` must be a filled ResidentSTDataset on
+    this device with the image and the ground truth; the loader itself is not iterated.  The ground truth never leaves the
+    device: the gaze cell is found by the kernel, with the summation order of the host's avg_pool2d.  ``chunk`` frames share
+    one forward; at ``chunk=1`` (the default) every launch is the file path's, so the pool equals what
+    ResidentLSTMDataset.fill reads from that path's files, bit for bit.  A batched forward is another tensor (the abs-max
+    scales are per tensor, the conv launches pick their geometry by batch size): ``chunk > 1`` is an opt-in that equals
+    model(batch) -> to_nhwc -> window_mean on the same batches, not the files."""
     dev = torch.device(device if str(device).startswith(('cuda', 'cpu')) else 'cuda:' + str(device))
+    if into is not None:
+        if shard is not None:
+            raise ValueError("extractw: into= with shard= is not supported (a sharded extraction leaves every rank with its "
+                             "own vectors only)")
+        if align:
+            raise ValueError("extractw: into= with align=True is not supported (the aligned window is a weight map built on "
+                             "the host from the full-resolution arg-max; the in-memory hand-over has no device form of it)")
+        if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f"extractw: chunk must be a positive integer, got {chunk!r}")
+        _check_into(getattr(loader, 'dataset', None), into, dev)
+        print('extracting lstm training data into device memory...')
+        # The file path creates one iterator over the loader, and creating it draws the loader's base seed from torch's global
+        # generator.  The same draw is made here (no sample is fetched), so that whatever is seeded after the extraction is
+        # what it is after the file path.
+        if getattr(loader, 'num_workers', None) == 0:
+            iter(loader)
+        _extract_into(loader, model, crop_size, dev, into, chunk)
+        print('done')
+        return
     second = _SecondFrame()
     if shard is not None:
         loader, second = _shard_loader(loader, shard), (lambda flag: True)
+    if savepath is None:
+        raise ValueError("extractw: savepath is needed (only into= writes no file)")
     print('extracting lstm training data...')
     os.makedirs(savepath, exist_ok=True)
     with torch.no_grad():
@@ -148,15 +246,22 @@ def extractw(loader, model, savepath, crop_size=3, device='0', align=False, shar
 
 
 def extract_LSTM_training_data(save_path='../512w', trained_model='save/best_fusion.pth.tar', device='0', crop_size=3,
-                               traindata=None, valdata=None, align=False, shard=None):
+                               traindata=None, valdata=None, align=False, shard=None, into=None, chunk=1):
+    """``into=(train_set, val_set)``: the two ResidentLSTMDataset.from_st sets that take the vectors in device memory
+    (extractw(into=...), ``chunk`` frames per forward); nothing is written under ``save_path``."""
+    if into is not None and len(into) != 2:
+        raise ValueError("extract_LSTM_training_data: into must be (train_set, val_set)")
     model = make_layers(cfg['D'], 3)
     sd = torch.load(trained_model, map_location='cpu', weights_only=False)['state_dict']
     own = model.state_dict()
     own.update({k[len('features_s.'):]: v for k, v in sd.items() if k.startswith('features_s.')})
     model.load_state_dict(own)
     model.to(torch.device('cuda:' + device)).eval()
-    for data, sub in ((traindata, 'train'), (valdata, 'test')):
+    for k, (data, sub) in enumerate(((traindata, 'train'), (valdata, 'test'))):
         loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
                             collate_fn=getattr(data, 'collate_fn', None))
+        if into is not None:
+            extractw(loader, model, None, crop_size, device, align, shard=shard, into=into[k], chunk=chunk)
+            continue
         extractw(loader, model, os.path.join(save_path, sub), crop_size, device, align, shard=shard)
     print('Attention weight for training LSTMnet successfully extracted.')

@@ -13,10 +13,31 @@ def build_parser():
     from .streamtrain import _CheckedParser, add_augment_flags
 
     class _Parser(_CheckedParser):
-        """Also refuses ``--late_handover`` where it cannot work, as any other bad command line."""
+        """Also refuses ``--late_handover`` and ``--lstm_handover`` where they cannot work, as any other bad command line."""
 
         def parse_known_args(self, args=None, namespace=None):
             ns, rest = super().parse_known_args(args, namespace)
+            if getattr(ns, 'lstm_handover_chunk', None) is not None and not getattr(ns, 'lstm_handover', False):
+                self.error("--lstm_handover_chunk needs --lstm_handover")
+            if getattr(ns, 'lstm_handover', False):
+                if not getattr(ns, 'gpu_resident', False):
+                    self.error("--lstm_handover needs --gpu_resident: the frames and the ground truth are taken from the "
+                               "resident pool on the device")
+                if not ns.extract_lstm:
+                    self.error("--lstm_handover needs --extract_lstm: the LSTM vectors exist only in the memory of the run "
+                               "that extracts them")
+                if not ns.train_lstm:
+                    self.error("--lstm_handover needs --train_lstm: the vectors are not written anywhere, only this run's "
+                               "LSTM training can use them")
+                if ns.align:
+                    self.error("--lstm_handover does not take --align: the aligned window is built on the host from the "
+                               "full-resolution ground truth")
+                if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+                    self.error("--lstm_handover runs in one process: a sharded extraction leaves every rank with its own "
+                               "vectors only (WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
+                if getattr(ns, 'lstm_handover_chunk', 1) < 1:
+                    self.error("--lstm_handover_chunk must be at least 1")
+                ns.lstm_resident = True
             if getattr(ns, 'late_handover', False):
                 if not getattr(ns, 'gpu_resident', False):
                     self.error("--late_handover needs --gpu_resident: the frames and the ground truth are taken from the "
@@ -91,6 +112,13 @@ def build_parser():
       help="with --gpu_resident --extract_late --train_late: the extraction writes the SP / AT planes and the ground truth "
            "straight into the late-fusion pools on the device (no pred / feat file is written or read) and LF trains from "
            "them.  Implies --late_resident; one process only.  Honours --gpu_resident_gb")
+    a('--lstm_handover', action='store_true', default=argparse.SUPPRESS,
+      help="with --gpu_resident --extract_lstm --train_lstm: the extraction writes the LSTM vectors straight into the vector "
+           "pools on the device (no fix_*.pth.tar file is written or read, --extract_lstm_path is not touched) and the LSTM "
+           "trains from them.  Implies --lstm_resident; one process only; not with --align.  Honours --gpu_resident_gb")
+    a('--lstm_handover_chunk', type=int, default=argparse.SUPPRESS,
+      help="frames per encoder forward of the --lstm_handover extraction (default 1: the file path's schedule, bit for bit; "
+           "a larger chunk is faster and is another batched forward, not bit-identical with the files)")
     add_augment_flags(p)                  # the SP stage's training loop only: validation, AT and LF never see an augmented batch
     return p
 
@@ -107,7 +135,8 @@ def _at_stage(args, STTrainData, STValData):
              lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
              device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
              task=args.task, align=args.align, resident=getattr(args, 'lstm_resident', False) and args.train_lstm,
-             resident_gb=getattr(args, 'gpu_resident_gb', None))
+             resident_gb=getattr(args, 'gpu_resident_gb', None), lstm_handover=getattr(args, 'lstm_handover', False),
+             lstm_handover_chunk=getattr(args, 'lstm_handover_chunk', 1))
     if args.train_lstm:
         att.train()
     if args.extract_late and getattr(args, 'late_handover', False):

@@ -151,6 +151,6 @@ from .flow import (  # noqa: E402,F401
     tvl1_flow, tvl1_iterate, tvl1_warp,
 )
 from .handover import (  # noqa: E402,F401
-    LATE_INPUT_STATUS, LATE_STORE_STATUS, _map_dev, check_late_store_status, draw_ring, late_input, late_input_status,
-    late_store, late_store_status,
+    LATE_INPUT_STATUS, LATE_STORE_STATUS, LSTM_STORE_STATUS, _map_dev, check_late_store_status, check_lstm_store_status,
+    draw_ring, late_input, late_input_status, late_store, late_store_status, lstm_store, lstm_store_status,
 )

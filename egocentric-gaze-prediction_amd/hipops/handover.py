@@ -1,5 +1,6 @@
 """The AT -> LF hand-over on the device (late_input: predict.py's; late_store: AT.extract_late(into=...)'s, straight into a
-resident late-fusion pool) and the gaze marker of an overlay (draw_ring)."""
+resident late-fusion pool), the SP -> AT hand-over (lstm_store: extractLSTMw.extractw(into=...)'s, straight into a resident
+LSTM vector pool) and the gaze marker of an overlay (draw_ring)."""
 from __future__ import annotations
 
 import sys
@@ -184,6 +185,101 @@ def check_late_store_status(st: int, who: str = "late_store", stacklevel: int = 
     if st:
         import warnings
         warnings.warn(f"{who}: {LATE_STORE_STATUS.get(st, st)}", RuntimeWarning, stacklevel=stacklevel)
+
+
+LSTM_STORE_STATUS = {1: "a ground-truth plane number or a pool row outside its pool (that sample wrote nothing)"}
+
+
+def lstm_store(feat_nhwc: torch.Tensor, gt_pool: torch.Tensor, gt_src: torch.Tensor, pool: torch.Tensor, dst: torch.Tensor,
+               size: int, cell: int = 16, want_cells: bool = False, status_to: Optional[dict] = None):
+    """The LSTM vectors of a chunk written straight into a resident vector pool (data.lstm_resident), in one launch
+    (egz_lstm_store): what extractLSTMw.channel_weight(feat, gt, size, align=False) computes per sample and extractw writes to
+    fix_<name>.pth.tar, bit for bit, without the ground truth leaving the device.
+
+    feat_nhwc: fp32 (B, H, W, C) channels-last, H == W (the reference clips both window coordinates with H).  gt_pool: uint8
+    (Q, H cell, W cell) with gt_src: int64 (B,), the plane of gt_pool that is each sample's ground truth.  pool: fp32 (rows, C)
+    with dst: int64 (B,), the row that takes each sample's vector; -1 skips the sample.  All contiguous and on one GPU, but
+    ``dst`` may be a host tensor: it is checked there and uploaded from pinned memory without waiting for the device; a device
+    ``dst`` is read back for the check (a wait).  A row named twice is refused.  The gaze cell is the first arg-max of
+    avg_pool2d(gt / 255, cell) in ATen's CPU summation order, the window extractLSTMw.var_window(cell, size), the mean
+    window_mean's.  A number outside [-1, rows) in ``dst`` or outside [0, Q) in ``gt_src`` is never dereferenced: that sample
+    writes nothing and bit 0 of the status word goes up.  The word is read here (a wait; bit 0 raises), or, with ``status_to``
+    (a dict), left there as ``(pinned host word, event)`` under '_lstm_store_status' for lstm_store_status.
+    -> pool, or (pool, cells) with ``want_cells``: cells int32 (B,), the flat gaze cell of every stored sample (-1: skipped)."""
+    what = "lstm_store"
+    for name, t in (("feat_nhwc", feat_nhwc), ("gt_pool", gt_pool), ("gt_src", gt_src), ("pool", pool), ("dst", dst)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
+    if not feat_nhwc.is_cuda:
+        raise ValueError(f"{what}: feat_nhwc must be a HIP ('cuda') tensor -- this package has no CPU path")
+    dev = feat_nhwc.device
+    if feat_nhwc.dtype != torch.float32 or feat_nhwc.dim() != 4 or min(feat_nhwc.shape) == 0:
+        raise ValueError(f"{what}: feat_nhwc must be a non-empty float32 (B, H, W, C), got {feat_nhwc.dtype} "
+                         f"{tuple(feat_nhwc.shape)}")
+    B, Hh, Ww, C = (int(v) for v in feat_nhwc.shape)
+    if Hh != Ww:
+        raise ValueError(f"{what}: a {Hh} x {Ww} map: H == W is needed (the reference clips both window coordinates with H)")
+    if B > 65535:
+        raise ValueError(f"{what}: {B} samples in one launch (65535 at most)")
+    for name, v, lo, hi in (("cell", cell, 1, 256), ("size", size, 1, Hh)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise ValueError(f"{what}: {name} must be an integer in {lo} .. {hi}, got {v!r}")
+    for name, t in (("gt_pool", gt_pool), ("gt_src", gt_src), ("pool", pool)):
+        if t.device != dev:
+            raise ValueError(f"{what}: {name} must be on the features' device {dev}, got {t.device}")
+    if gt_pool.dtype != torch.uint8 or gt_pool.dim() != 3 or gt_pool.shape[0] == 0:
+        raise ValueError(f"{what}: gt_pool must be a non-empty uint8 (Q, H, W), got {gt_pool.dtype} {tuple(gt_pool.shape)}")
+    if tuple(gt_pool.shape[1:]) != (Hh * cell, Ww * cell):
+        raise ValueError(f"{what}: gt_pool holds planes of {tuple(gt_pool.shape[1:])}, a {Hh} x {Ww} map with cell {cell} "
+                         f"needs {(Hh * cell, Ww * cell)}")
+    if pool.dtype != torch.float32 or pool.dim() != 2 or pool.shape[0] == 0:
+        raise ValueError(f"{what}: pool must be a non-empty float32 (rows, C), got {pool.dtype} {tuple(pool.shape)}")
+    if pool.shape[1] != C:
+        raise ValueError(f"{what}: pool rows hold {pool.shape[1]} values, feat_nhwc has C = {C} channels")
+    if gt_src.dtype != torch.int64 or tuple(gt_src.shape) != (B,):
+        raise ValueError(f"{what}: gt_src must be an int64 ({B},) tensor, got {gt_src.dtype} {tuple(gt_src.shape)}")
+    if dst.dtype != torch.int64 or tuple(dst.shape) != (B,) or not (dst.device == dev or dst.device.type == 'cpu'):
+        raise ValueError(f"{what}: dst must be an int64 ({B},) tensor on {dev} or on the host, got {dst.dtype} "
+                         f"{tuple(dst.shape)} on {dst.device}")
+    for name, t in (("feat_nhwc", feat_nhwc), ("gt_pool", gt_pool), ("gt_src", gt_src), ("pool", pool), ("dst", dst)):
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
+    named = dst.cpu().numpy()                                                     # (a device dst: a wait)
+    named = named[named != -1]
+    if len(set(named.tolist())) != named.size:
+        seen = set()
+        twice = next(int(v) for v in named.tolist() if v in seen or seen.add(v))
+        raise ValueError(f"{what}: dst names row {twice} twice in one call")
+    if dst.device.type == 'cpu':
+        pinned = torch.empty((B,), dtype=torch.int64, pin_memory=True)
+        pinned.copy_(dst)
+        dst = pinned.to(dev, non_blocking=True)
+    cells = torch.full((B,), -1, dtype=torch.int32, device=dev) if want_cells else None
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(LIB.egz_lstm_store(feat_nhwc.data_ptr(), B, Hh, Ww, C, gt_pool.data_ptr(), gt_pool.shape[0], gt_src.data_ptr(), cell,
+                             size, pool.data_ptr(), pool.shape[0], dst.data_ptr(), _p(cells), status.data_ptr(), _stream()),
+          "egz_lstm_store")
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to['_lstm_store_status'] = (host, done)
+    else:
+        _H.check_lstm_store_status(_H.lstm_store_status((host, done)))
+    return (pool, cells) if want_cells else pool
+
+
+def lstm_store_status(pending) -> int:
+    """Waits for the lstm_store launch that ``pending = (host status word, event)`` belongs to -> its status word
+    (LSTM_STORE_STATUS names the bit)."""
+    return _H.late_input_status(pending)
+
+
+def check_lstm_store_status(st: int, who: str = "lstm_store"):
+    """The rule for an lstm_store status word: bit 0 (samples were skipped) raises."""
+    if st & 1:
+        raise RuntimeError(f"{who}: {LSTM_STORE_STATUS[1]}")
 
 
 def draw_ring(images: torch.Tensor, centers: torch.Tensor, r_in: int, r_out: int, colour=(255, 255, 255)) -> torch.Tensor:

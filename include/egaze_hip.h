@@ -548,6 +548,21 @@ int egz_late_gather(const unsigned char* pool, long P, const long* table, long N
 int egz_lstm_pool_fetch(const float* pool, long rows, int width, const int* in_row, const int* tgt_row,
                         const unsigned char* reset, long n_steps, int* cursor, float* inp, float* tgt, float* state,
                         long state_n, unsigned int* status, hipStream_t stream);
+/* The SP -> AT hand-over written into such a pool on the device (extractLSTMw.extractw(into=...), csrc/lstm_pool.hip): for
+ * every sample b of an encoder forward, the vector the file path stores in fix_<name>.pth.tar.  feat (B, H, W, C) fp32
+ * channels-last, H == W; gt_pool (Q, H cell, W cell) uint8 and gt_src (B,) int64: sample b's ground truth is plane gt_src[b];
+ * pool (rows, C) fp32 and dst (B,) int64: the row that takes sample b's vector, -1 skips the sample (nothing of it is read).
+ * Gaze cell = the first arg-max of avg_pool2d(u8 / 255, cell) as ATen's CPU kernel computes it: per cell s = 0.f, s += (float)u
+ * / 255.f over its cell x cell bytes in row-major order, s / (float)(cell cell); on equal scores the lower cell.  Window =
+ * extractLSTMw.var_window(gaze cell, size) (both coordinates clipped with H); pool[dst[b]][c] = the window mean of channel c
+ * with egz_window_mean's arithmetic.  cells (B,) int32, optional (null: not written): the flat gaze cell of every stored
+ * sample.  A gt_src[b] outside [0, Q) or a dst[b] outside [-1, rows) is never turned into an address: that sample writes
+ * nothing and *status (device, zero-filled by the caller; a sticky OR) gets bit 0.  1 <= B <= 65535, 1 <= H == W <= 1024,
+ * 1 <= cell <= 256, 1 <= size <= H, C, Q, rows >= 1, every pointer but cells required: anything else returns an error and
+ * launches nothing.  The rows named in one call must be distinct.  No allocation, no synchronisation. */
+int egz_lstm_store(const float* feat, int B, int H, int W, int C, const unsigned char* gt_pool, long Q, const long* gt_src,
+                   int cell, int size, float* pool, long rows, const long* dst, int* cells, unsigned int* status,
+                   hipStream_t stream);
 /* AT extraction glue (AT.py:25-39,58-66,229; extractLSTMw.py:81-90): chn_weight = mean of the size x size window of the
  * channels-last (B,H,W,C) feature map around gaze_point / cell; weighted map = min-max normalised sum_c feat * w. */
 int egz_crop_mean(const float* feat, const int* gp, float* out, int B, int H, int W, int C, int size, int cell,
