@@ -150,6 +150,7 @@ SIGNATURES = {
     "egz_jpeg_encode_ws_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "egz_jpeg_encode": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_size_t, P, c_int, S]),
     "egz_jpeg_encode_write": (c_int, [P, c_size_t, c_int, c_int, c_int, c_int, P, c_long, P, P, P, P, S]),
+    "egz_jpeg_roundtrip": (c_int, [P, c_long, c_int, c_int, c_int, P, P, c_long, P, S]),
     # --- TV-L1 optical flow (csrc/flow_tvl1.hip)
     "egz_tvl1_default_k": (c_int, []),
     "egz_bgr_to_gray_u8": (c_int, [P, c_int, c_int, c_int, c_int, P, S]),

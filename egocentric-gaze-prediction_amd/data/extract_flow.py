@@ -13,12 +13,17 @@ with one read-back of the encoded bytes per chunk.  ``flow_x_%05d.jpg`` / ``flow
 n to the next frame, n being the number in the first frame's name (counted from 1): the last frame of a folder gets no flow, and
 ``STdatas.build_temporal_list`` reads the ten flows that end at a frame's number.  An output file that exists is kept unless
 ``--overwrite`` is given.  The algorithm, its parameters, ``bound`` and this numbering are defined in DESIGN.md ("TV-L1 optical
-flow"); agreement with the external tool's own files is not verified.  Video decoding is out of scope: the input is frames."""
+flow"); agreement with the external tool's own files is not verified.  Video decoding is out of scope: the input is frames.
+
+``flows_into`` is the same chain without the files: it writes the flow images straight into the flow planes of resident
+datasets on the device (``gaze_full --gpu_resident --flow_handover``)."""
 import argparse
 import os
 import re
 
 FLOW_NAMES = ('flow_x_%05d.jpg', 'flow_y_%05d.jpg')
+# TV-L1 parameters of the command line, and of flows_into when it is given none
+TVL1_DEFAULTS = {'tau': 0.25, 'lam': 0.15, 'theta': 0.3, 'zfactor': 0.5, 'nscales': 5, 'warps': 5, 'iterations': 30}
 
 
 def list_frames(folder):
@@ -114,6 +119,96 @@ def process_folder(src, dst, args, device='cuda'):
     return written
 
 
+# ----------------------------------------------------------------------------- hand-over into the resident ST pool (no files)
+def flow_key(path):
+    """A flow path of STdatas.build_temporal_list, used as a key only -> (folder name, 0 for x / 1 for y, number)."""
+    m = re.fullmatch(r'flow_([xy])_(\d+)\.jpg', os.path.basename(path))
+    if not m:
+        raise ValueError(f"{path}: not a flow_x_%05d.jpg / flow_y_%05d.jpg name")
+    return os.path.basename(os.path.dirname(path)), 'xy'.index(m.group(1)), int(m.group(2))
+
+
+def missing_frame(numbers, n):
+    """The frame whose absence makes flow ``n`` unavailable from the frames ``numbers`` (a set), or None: flow n runs from
+    frame n to frame n + 1."""
+    return n if n not in numbers else (n + 1 if n + 1 not in numbers else None)
+
+
+def wanted_ranges(frames, wanted, chunk):
+    """process_folder's chunk ranges over ``frames`` (list_frames' result) that hold at least one flow number of ``wanted``:
+    the ranges of the others are neither decoded nor computed, as its ``todo`` skips ranges whose files all exist."""
+    return [(first, last) for first, last in chunk_ranges(len(frames), chunk)
+            if any(frames[i][0] in wanted for i in range(first, last))]
+
+
+def flows_into(datasets, framePath, device, size=None, bound=20.0, quality=95, chunk=32, params=None):
+    """Computes the flow images the filled ``datasets`` (data.resident.ResidentSTDatasets planned with ``flow_from``) refer
+    to and writes them into the planes their plans gave to the flow paths, without a file: per video folder the chunk ranges
+    of process_folder, the same chain up to flow_to_u8, then ONE hipops.jpeg_roundtrip launch per chunk and pool in place of
+    jpeg_encode -> file -> read -> jpeg_decode -- the same bytes (the entropy coding is lossless; the quantisation is kept).
+    ``quality`` 0 stores the flow_to_u8 planes as they are.  A flow no sample refers to gets no plane, a range in which none
+    is referred to is neither decoded nor computed.  ``size`` (H, W): the frames are resized to it first; default: the
+    pools' plane size.  The device is waited for once, at the end, for the status words (not at all with quality 0).
+    -> {'pairs': frame pairs computed, 'planes': planes written, 'files': 0}."""
+    import torch
+    from .. import hipops
+    if chunk < 1:
+        raise ValueError("flows_into: chunk must be at least 1")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 0 <= quality <= 100:
+        raise ValueError(f"flows_into: quality {quality!r} outside 0 .. 100 (0: no JPEG round trip)")
+    params = dict(TVL1_DEFAULTS if params is None else params)
+    datasets = [ds for ds in datasets if len(ds) and getattr(ds, 'flow_keys', None)]
+    for ds in datasets:
+        if ds.pool is None:
+            raise RuntimeError("flows_into: fill(device, flow_from=...) has not run (the pool is not on the device)")
+    hws = {tuple(ds.hw) for ds in datasets}
+    if len(hws) > 1:
+        raise RuntimeError(f"flows_into: the pools hold planes of different sizes {sorted(hws)}")
+    if size is None and hws:
+        size = next(iter(hws))
+    wanted = {}                             # folder -> {number -> [(dataset index, 0 x / 1 y, plane)]}
+    for k, ds in enumerate(datasets):
+        for path, plane in ds.flow_keys:
+            folder, c, n = flow_key(path)
+            wanted.setdefault(folder, {}).setdefault(n, []).append((k, c, plane))
+    counts = {'pairs': 0, 'planes': 0, 'files': 0}
+    statuses = []
+    for folder in sorted(wanted):
+        src = os.path.join(framePath, folder)
+        frames = list_frames(src)
+        want = wanted[folder]
+        for first, last in wanted_ranges(frames, want, chunk):
+            bgr = decode_frames([os.path.join(src, frames[i][1]) for i in range(first, last + 1)], size, device)
+            u8 = flow_images(bgr, bound, params)
+            n = last - first
+            u8 = u8.reshape((2 * n,) + tuple(u8.shape[-2:]))
+            counts['pairs'] += n
+            per_pool = {}
+            for i in range(n):
+                for k, c, plane in want.get(frames[first + i][0], ()):
+                    per_pool.setdefault(k, []).append((c * n + i, plane))
+            for k, pairs in per_pool.items():
+                pool = datasets[k].pool
+                if tuple(u8.shape[-2:]) != tuple(pool.shape[-2:]):
+                    raise RuntimeError(f"{src}: flow images of {tuple(u8.shape[-2:])} pixels, the pool holds planes of "
+                                       f"{tuple(pool.shape[-2:])}")
+                sel = [s for s, _ in pairs]
+                dst = torch.tensor([p for _, p in pairs], dtype=torch.int64).to(pool.device, non_blocking=True)
+                planes = u8 if sel == list(range(2 * n)) else \
+                    u8.index_select(0, torch.tensor(sel, dtype=torch.int64).to(u8.device, non_blocking=True))
+                if quality:
+                    statuses.append(hipops.jpeg_roundtrip(planes, quality, out=pool, plane_index=dst)[1])
+                else:
+                    pool.index_copy_(0, dst, planes)
+                counts['planes'] += len(pairs)
+    if statuses:
+        bad = torch.cat(statuses).cpu()     # the one wait
+        if int(bad.abs().max()):
+            raise RuntimeError(f"flows_into: jpeg_roundtrip status {sorted(set(bad.tolist()))}: "
+                               f"{hipops.JPEG_ROUNDTRIP_STATUS[1]}")
+    return counts
+
+
 def build_parser():
     p = argparse.ArgumentParser(description="TV-L1 optical-flow images (flow_x_*.jpg, flow_y_*.jpg) of folders of frames, "
                                             "computed on the GPU")
@@ -127,10 +222,8 @@ def build_parser():
     a('--folders', nargs='*', default=None, help="sub-folders to process (default: all)")
     a('--overwrite', action='store_true', help="recompute and replace output files that exist")
     a('--device', default='cuda', help="torch device")
-    for name, default in (('tau', 0.25), ('lam', 0.15), ('theta', 0.3), ('zfactor', 0.5)):
-        a('--' + name, type=float, default=default, help=f"TV-L1 parameter (default {default})")
-    for name, default in (('nscales', 5), ('warps', 5), ('iterations', 30)):
-        a('--' + name, type=int, default=default, help=f"TV-L1 parameter (default {default})")
+    for name, default in TVL1_DEFAULTS.items():
+        a('--' + name, type=type(default), default=default, help=f"TV-L1 parameter (default {default})")
     return p
 
 

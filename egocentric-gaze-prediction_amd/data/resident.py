@@ -9,8 +9,10 @@ A sample of this dataset is its number; the collated batch carries the numbers a
 points (data.STdatas.stage_batch / to_raw_u8, streamtrain.stage_stream) turn it into tensors.  The DataLoader, its samplers and
 their RNG draws are those of the host dataset, so a seeded run visits the same samples in the same batches."""
 import contextlib
+import os
 import time
 import warnings
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -19,6 +21,16 @@ from ._io import imread
 from .STdatas import STDataset, sniff
 
 COLS = 22                                   # table columns: image, 20 flow planes, ground truth
+
+
+class FlowFrom(NamedTuple):
+    """Where the flow planes of a resident dataset come from when not from files: data.extract_flow.flows_into computes them
+    from the frames under ``framePath`` (one folder per video, img_%05d.jpg) with these arguments of its own."""
+    framePath: str
+    bound: float = 20.0
+    quality: int = 95
+    chunk: int = 32
+    params: Optional[dict] = None
 
 
 # ----------------------------------------------------------------------------- the one-time fill, shared by the resident datasets
@@ -45,14 +57,17 @@ def _size_of(path, channels):
     return tuple(size) if size is not None else tuple(_host_decode(path, channels).shape[1:])
 
 
-def fill_pool(files, hw, decode, device, chunk):
+def fill_pool(files, hw, decode, device, chunk, planes=None):
     """Decodes ``files`` [(path, first plane, channels)], ``chunk`` files at a time, straight into their planes of a new uint8
-    (planes, h, w) pool on ``device``: decode='gpu' sends the files ``sniff`` takes through hipops.jpeg_decode, everything else
+    (planes, h, w) pool on ``device`` (``planes`` None: up to the last file's; planes no file names stay undefined -- the
+    flow planes of a dataset planned with ``flow_from``, which flows_into writes): decode='gpu' sends the files ``sniff`` takes through hipops.jpeg_decode, everything else
     goes through _io.imread and a pinned staging buffer.  Corrupt data warns, naming the file; an unsupported, unreadable or
     wrongly sized file raises, naming it.  -> the pool; the work may still be in flight on the current stream."""
     from .. import hipops as H
     h, w = hw
-    pool = torch.empty((files[-1][1] + files[-1][2], h, w), dtype=torch.uint8, device=device)
+    pool = torch.empty((files[-1][1] + files[-1][2] if planes is None else planes, h, w), dtype=torch.uint8, device=device)
+    if not files:
+        return pool
     stage = torch.empty((min(chunk, len(files)) * max(f[2] for f in files), h, w), dtype=torch.uint8, pin_memory=True)
     pending = []                            # (host status words, event, paths) of the decode launches in flight
     for c0 in range(0, len(files), chunk):
@@ -114,12 +129,14 @@ def fill_planned(ds, device, budget_bytes, chunk, who, flag):
                            f"({ds.planes} planes of {ds.hw[0]} x {ds.hw[1]}), {budget_bytes} bytes are allowed: "
                            f"run without {flag} (there is no partial cache)")
     t0 = time.perf_counter()
-    pool = fill_pool(ds.files, ds.hw, ds.decode, device, chunk)
+    skip = {path for path, _ in getattr(ds, 'flow_keys', ())}     # planned with flow_from: keys, not files
+    files = [f for f in ds.files if f[0] not in skip] if skip else ds.files
+    pool = fill_pool(files, ds.hw, ds.decode, device, chunk, planes=ds.planes)
     ds.table = ds.plane_table.to(device)
     torch.cuda.synchronize(device)          # the gathers run on other streams (staged_batches' copy stream)
     ds.pool = pool
     ds.fill_seconds = time.perf_counter() - t0
-    print(f"resident dataset: {len(ds.files)} files decoded ({ds.decode}) into {ds.planes} planes, "
+    print(f"resident dataset: {len(files)} files decoded ({ds.decode}) into {ds.planes} planes, "
           f"{ds.needed_bytes} bytes on {device}, {ds.fill_seconds:.2f} s")
     return ds
 
@@ -136,13 +153,19 @@ class ResidentSTDataset(STDataset):
         self.collate_fn = self._collate
         self.pool = self.table = None       # device tensors after fill()
         self._plan = None
+        self.flow_from = None               # a FlowFrom: the flow paths are keys, flows_into fills their planes
+        self.flow_keys = []                 # [(flow path, plane)] under flow_from
+        self.flow_counts = None             # flows_into's counts after such a fill
         self._augment = None                # (AugSpec, epoch) inside augmenting()
 
     # ------------------------------------------------------------------ plan (host only)
     def plan(self):
         """Lists the distinct files of the fields in use, gives each its planes in the pool and builds the (N, 22) table of
         plane numbers (-1 in the columns of a field not in use).  Reads one file header for the plane size; touches no device.
-        Sets ``files`` [(path, first plane, channels)], ``planes``, ``hw``, ``plane_table`` (host) and ``needed_bytes``."""
+        Sets ``files`` [(path, first plane, channels)], ``planes``, ``hw``, ``plane_table`` (host) and ``needed_bytes``.
+        With ``flow_from`` the flow paths are listed and given planes all the same -- table and bytes are those of the plan
+        over files -- but as keys (``flow_keys``): no flow file is opened, and a sample whose stack needs a flow the frames
+        cannot give is refused here, before anything is allocated."""
         fields = tuple(self.gpu_fields)
         N = len(self)
         table = np.full((N, COLS), -1, dtype=np.int64)
@@ -167,13 +190,43 @@ class ResidentSTDataset(STDataset):
                 table[i, 21] = plane_of(self._files(i)[21], 1)
         if not files:
             raise RuntimeError("ResidentSTDataset.plan: no files (an empty dataset or no field in gpu_fields)")
+        self.flow_keys = []
+        if self.flow_from is not None and 'flow' in fields:
+            self._check_flows(table)
+            flow_planes = set(table[:, 1:21].flatten().tolist())
+            self.flow_keys = [(path, p) for path, p, _ in files if p in flow_planes]
         self.files = files
         self.planes = files[-1][1] + files[-1][2]
-        self.hw = self._size_of(files[0][0], files[0][2])
+        keys = {path for path, _ in self.flow_keys}
+        sized = next((f for f in files if f[0] not in keys), None)
+        self.hw = self._size_of(sized[0], sized[2]) if sized is not None else self._frame_size()
         self.plane_table = torch.from_numpy(table)
         self.needed_bytes = self.planes * self.hw[0] * self.hw[1] + table.nbytes
         self._plan = fields
         return self
+
+    def _check_flows(self, table):
+        """Refuses the first sample one of whose flows the frames under ``flow_from.framePath`` cannot give: flow n runs from
+        frame n to frame n + 1 (extract_flow's numbering), so both must be there."""
+        from .extract_flow import flow_key, list_frames, missing_frame
+        numbers = {}
+        for i in range(len(self)):
+            for path in self._files(i)[1:21]:
+                folder, _, n = flow_key(path)
+                if folder not in numbers:
+                    src = os.path.join(self.flow_from.framePath, folder)
+                    numbers[folder] = {k for k, _ in list_frames(src)} if os.path.isdir(src) else set()
+                miss = missing_frame(numbers[folder], n)
+                if miss is not None:
+                    raise RuntimeError(f"ResidentSTDataset.plan: sample {i} ({self.listGtFiles[i]}) needs "
+                                       f"{os.path.basename(path)} of {folder}, which the frames cannot give: "
+                                       f"{os.path.join(self.flow_from.framePath, folder, 'img_%05d.jpg' % miss)} is missing")
+
+    def _frame_size(self):
+        """Plane size of a plan that holds flow keys only: the first frame's."""
+        from .extract_flow import flow_key, list_frames
+        src = os.path.join(self.flow_from.framePath, flow_key(self.flow_keys[0][0])[0])
+        return self._size_of(os.path.join(src, list_frames(src)[0][1]), 3)
 
     _read, _host_decode = staticmethod(_read), staticmethod(_host_decode)
 
@@ -181,14 +234,20 @@ class ResidentSTDataset(STDataset):
         return _size_of(path, channels)
 
     # ------------------------------------------------------------------ fill (decode once)
-    def fill(self, device, budget_bytes=None, chunk=704):
+    def fill(self, device, budget_bytes=None, chunk=704, flow_from=None, run_flows=True):
         """Decodes every distinct file once, ``chunk`` files at a time, straight into its planes of the pool on ``device``.
         ``budget_bytes`` None: 0.8 x the free device memory.  A pool that does not fit raises before anything is allocated
         (there is no partial cache).  Corrupt data warns, naming the file; an unsupported, unreadable or wrongly sized file
-        raises, naming it.  Prints the number of files, the bytes and the seconds once."""
-        if self._plan != tuple(self.gpu_fields):
+        raises, naming it.  Prints the number of files, the bytes and the seconds once.  ``flow_from`` (a FlowFrom): the flow
+        planes are not decoded from files but computed from the frames by data.extract_flow.flows_into, here unless
+        ``run_flows`` is False (fill_all runs it once for all its datasets); its counts are left in ``flow_counts``."""
+        if self._plan != tuple(self.gpu_fields) or flow_from != self.flow_from:
+            self.flow_from = flow_from
             self.plan()
-        return fill_planned(self, device, budget_bytes, chunk, "ResidentSTDataset.fill", "--gpu_resident")
+        fill_planned(self, device, budget_bytes, chunk, "ResidentSTDataset.fill", "--gpu_resident")
+        if flow_from is not None and run_flows:
+            run_flows_into([self], device, flow_from)
+        return self
 
     # ------------------------------------------------------------------ samples
     def __getitem__(self, index):
@@ -242,12 +301,29 @@ class ResidentSTDataset(STDataset):
         return H.resident_gather(self.pool, self.table, idx, fields=fields, raw=raw, prepare=prepare, status_to=sample)
 
 
-def fill_all(datasets, device, budget_gb=None, flag="--gpu_resident"):
+def run_flows_into(datasets, device, flow_from):
+    """flows_into over filled ``datasets`` with the record's arguments; leaves the counts on each and prints them once."""
+    from .extract_flow import flows_into
+    t0 = time.perf_counter()
+    counts = flows_into(datasets, flow_from.framePath, device, bound=flow_from.bound, quality=flow_from.quality,
+                        chunk=flow_from.chunk, params=flow_from.params)
+    for ds in datasets:
+        ds.flow_counts = counts
+    print(f"flow hand-over: {counts['pairs']} frame pairs computed, {counts['planes']} planes written, "
+          f"{counts['files']} files, {time.perf_counter() - t0:.2f} s")
+    return counts
+
+
+def fill_all(datasets, device, budget_gb=None, flag="--gpu_resident", flow_from=None):
     """Fills several resident datasets (the training and the validation set of a script; ResidentSTDatasets,
     ResidentLateDatasets or a mix) under ONE budget: ``budget_gb`` GB, or 0.8 x the free memory of ``device``.  All are planned
-    first, so a set that does not fit raises before any pool is allocated.  ``flag``: the CLI switch the refusal names."""
+    first, so a set that does not fit raises before any pool is allocated.  ``flag``: the CLI switch the refusal names.
+    ``flow_from`` (a FlowFrom, ResidentSTDatasets only): the flow planes of all of them are computed from the frames in one
+    flows_into pass after the fills."""
     datasets = [ds for ds in datasets if len(ds)]
     for ds in datasets:
+        if flow_from is not None:
+            ds.flow_from = flow_from
         ds.plan()
     budget = int(budget_gb * 1e9) if budget_gb is not None else int(0.8 * torch.cuda.mem_get_info(torch.device(device))[0])
     needed = sum(ds.needed_bytes for ds in datasets)
@@ -255,5 +331,10 @@ def fill_all(datasets, device, budget_gb=None, flag="--gpu_resident"):
         raise RuntimeError(f"{flag}: the decoded datasets need {needed} bytes, {budget} bytes are allowed: "
                            f"run without {flag} (there is no partial cache)")
     for ds in datasets:
-        ds.fill(device, budget_bytes=budget)
+        if flow_from is not None:
+            ds.fill(device, budget_bytes=budget, flow_from=flow_from, run_flows=False)
+        else:
+            ds.fill(device, budget_bytes=budget)
         budget -= ds.needed_bytes
+    if flow_from is not None:
+        run_flows_into(datasets, device, flow_from)

@@ -13,7 +13,8 @@ def build_parser():
     from .streamtrain import _CheckedParser, add_augment_flags
 
     class _Parser(_CheckedParser):
-        """Also refuses ``--late_handover`` and ``--lstm_handover`` where they cannot work, as any other bad command line."""
+        """Also refuses ``--late_handover``, ``--lstm_handover`` and ``--flow_handover`` where they cannot work, as any other
+        bad command line."""
 
         def parse_known_args(self, args=None, namespace=None):
             ns, rest = super().parse_known_args(args, namespace)
@@ -52,6 +53,23 @@ def build_parser():
                     self.error("--late_handover runs in one process: a sharded extraction leaves every rank with its own "
                                "chunks only (WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
                 ns.late_resident = True
+            for flag in ('framePath', 'flow_quality', 'flow_bound'):
+                if getattr(ns, flag, None) is not None and not getattr(ns, 'flow_handover', False):
+                    self.error(f"--{flag} needs --flow_handover")
+            if getattr(ns, 'flow_handover', False):
+                if not getattr(ns, 'gpu_resident', False):
+                    self.error("--flow_handover needs --gpu_resident: the flow images are written into the resident pool on "
+                               "the device")
+                if getattr(ns, 'framePath', None) is None:
+                    self.error("--flow_handover needs --framePath: the flow images are computed from the frames "
+                               "(one folder per video, img_%05d.jpg)")
+                if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+                    self.error("--flow_handover runs in one process: every rank would compute every flow "
+                               "(WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
+                if not 0 <= getattr(ns, 'flow_quality', 95) <= 100:
+                    self.error("--flow_quality must be 0 .. 100 (0: no JPEG round trip)")
+                if not getattr(ns, 'flow_bound', 20.0) > 0:
+                    self.error("--flow_bound must be positive")
             return ns, rest
 
     p = _Parser()
@@ -119,6 +137,16 @@ def build_parser():
     a('--lstm_handover_chunk', type=int, default=argparse.SUPPRESS,
       help="frames per encoder forward of the --lstm_handover extraction (default 1: the file path's schedule, bit for bit; "
            "a larger chunk is faster and is another batched forward, not bit-identical with the files)")
+    a('--flow_handover', action='store_true', default=argparse.SUPPRESS,
+      help="with --gpu_resident --framePath P: the TV-L1 flow images are computed from the frames and written straight into "
+           "the flow planes of the resident pool (data.extract_flow.flows_into); no flow file is written or read and "
+           "--flowPath is not opened.  The planes are those extract_flow's files decode to.  One process only")
+    a('--framePath', default=argparse.SUPPRESS,
+      help="--flow_handover: folder of per-video folders holding img_%%05d.jpg frames (extract_flow's --framePath)")
+    a('--flow_quality', type=int, default=argparse.SUPPRESS,
+      help="--flow_handover: JPEG quality the flow images go through (default 95, extract_flow's; 0: none)")
+    a('--flow_bound', type=float, default=argparse.SUPPRESS,
+      help="--flow_handover: flow of +-bound pixels maps to 255 / 0 (default 20, extract_flow's)")
     add_augment_flags(p)                  # the SP stage's training loop only: validation, AT and LF never see an augmented batch
     return p
 
@@ -242,7 +270,12 @@ def main(argv=None):
         # would spin for hours and need a multi-day collective timeout that also hides real hangs of the SP / LF all-reduces
         torch.distributed.init_process_group(os.environ.get('EGAZE_DIST_BACKEND', 'nccl'),
                                              timeout=datetime.timedelta(minutes=30))
-    listFolders = sorted(os.listdir(args.flowPath))
+    flow_from = None
+    if getattr(args, 'flow_handover', False):   # the flow paths are keys into the pool; --flowPath is never opened
+        from .data.resident import FlowFrom
+        flow_from = FlowFrom(args.framePath, bound=getattr(args, 'flow_bound', 20.0),
+                             quality=getattr(args, 'flow_quality', 95))
+    listFolders = sorted(os.listdir(args.framePath if flow_from is not None else args.flowPath))
     listGtFiles, listValGtFiles = _split(args.gtPath, args.val_name)
     print('num of training samples: ', len(listGtFiles))
     listfixsacTrain, listfixsacVal = _split(args.fixsacPath, args.val_name)
@@ -257,7 +290,8 @@ def main(argv=None):
     STValData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
                           listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
     if resident:
-        fill_all((STTrainData, STValData), torch.device('cuda:' + args.device), getattr(args, 'gpu_resident_gb', None))
+        fill_all((STTrainData, STValData), torch.device('cuda:' + args.device), getattr(args, 'gpu_resident_gb', None),
+                 flow_from=flow_from)
     os.makedirs(args.save_path, exist_ok=True)
     if args.train_sp:
         sp = SP(lr=args.lr, loss_save=args.sp_save_img, save_name=args.save_sp, save_path=args.save_path,

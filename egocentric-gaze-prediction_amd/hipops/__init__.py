@@ -139,7 +139,7 @@ from .dataprep import (  # noqa: E402,F401
 )
 from .jpeg import (  # noqa: E402,F401
     JPEG_ENCODE_STATUS, JPEG_STATUS, _SUBSAMPLING, _dev_table, _jpeg_encode_args, _jpeg_encode_scan, jpeg_decode,
-    jpeg_encode, jpeg_encode_into,
+    jpeg_encode, jpeg_encode_into, JPEG_ROUNDTRIP_STATUS, jpeg_roundtrip,
 )
 from .vis import (  # noqa: E402,F401
     _JET, _JET_WARNED, _LINEAR_T, _linear_tables, _u8_dev, cell_argmax_u8, heatmap_overlay, jet_lut,

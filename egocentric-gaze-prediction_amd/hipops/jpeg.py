@@ -1,4 +1,4 @@
-"""Baseline JPEG decode and encode."""
+"""Baseline JPEG decode and encode, and the round trip through both without the bitstream."""
 from __future__ import annotations
 
 import sys
@@ -161,3 +161,56 @@ def jpeg_encode_into(images: torch.Tensor, out: torch.Tensor, slot_offsets, slot
     check(LIB.egz_jpeg_encode_write(ws.data_ptr(), nb, N, H, W, C, out.data_ptr(), out.numel(), so.data_ptr(), sc.data_ptr(),
                                     lengths.data_ptr(), status.data_ptr(), _stream()), "egz_jpeg_encode_write")
     return lengths, status
+
+
+# ----------------------------------------------------------------------------- JPEG round trip (flow hand-over, predict)
+JPEG_ROUNDTRIP_STATUS = {0: "ok", 1: "the plane index is outside the destination (nothing of the plane was written)"}
+
+
+def jpeg_roundtrip(planes: torch.Tensor, quality: int = 95, out: torch.Tensor = None, plane_index=None):
+    """The planes jpeg_decode gives for jpeg_encode(planes, quality), bit for bit, in one launch (egz_jpeg_roundtrip): per
+    8x8 block FDCT, quantisation, dequantisation, IDCT.  The entropy coding between the two is lossless and is left out, so
+    there is no bitstream, no workspace and no read-back.
+
+    planes: (N, H, W) uint8 on the GPU.  -> (out, status): ``out`` is a new (N, H, W) tensor, or the caller's (uint8,
+    contiguous, on the same GPU), read as whole H x W planes: plane i goes to plane plane_index[i] (default i; a list or a
+    tensor on either device).  status (N,) int32 on the GPU (JPEG_ROUNDTRIP_STATUS): 1 where the index is outside ``out`` --
+    that plane is not written.  ``out`` may be ``planes`` itself with the default index (in place); any other overlap of
+    ``out`` with ``planes`` is refused."""
+    if not isinstance(planes, torch.Tensor) or not planes.is_cuda:
+        raise RuntimeError("jpeg_roundtrip: planes: expected a HIP ('cuda') tensor -- this package has no CPU path")
+    if planes.dtype != torch.uint8:
+        raise ValueError(f"jpeg_roundtrip: planes must be uint8, got {planes.dtype}")
+    if planes.dim() != 3:
+        raise ValueError(f"jpeg_roundtrip: planes of shape {tuple(planes.shape)}: expected (N, H, W) grey planes")
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"jpeg_roundtrip: quality {quality!r} outside 1 .. 100")
+    N, H, W = (int(v) for v in planes.shape)
+    if not (0 < H <= 4096 and 0 < W <= 4096):
+        raise ValueError(f"jpeg_roundtrip: planes of {H} x {W}: height and width must be 1 .. 4096")
+    if N < 1:
+        raise ValueError("jpeg_roundtrip: planes holds no plane")
+    dev = planes.device
+    src = planes.contiguous()
+    if out is None:
+        if plane_index is not None:
+            raise ValueError("jpeg_roundtrip: plane_index= needs out=")
+        out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or not out.is_cuda or not out.is_contiguous() \
+            or out.numel() % (H * W) or not out.numel() or out.device != dev:
+        raise ValueError(f"jpeg_roundtrip: out must be a contiguous uint8 GPU tensor of whole {H} x {W} planes on {dev}")
+    pl = None
+    if plane_index is not None:
+        pl = _dev_table(plane_index, torch.int64, dev, "plane_index")
+        if pl.numel() != N:
+            raise ValueError(f"jpeg_roundtrip: {N} planes but {pl.numel()} plane indices")
+    nbytes = N * H * W
+    lo, hi = max(src.data_ptr(), out.data_ptr()), min(src.data_ptr() + nbytes, out.data_ptr() + out.numel())
+    if lo < hi and not (pl is None and src.data_ptr() == out.data_ptr()):
+        raise ValueError("jpeg_roundtrip: out overlaps planes: only out = planes itself with the default plane_index (in "
+                         "place) is supported")
+    status = torch.empty(N, dtype=torch.int32, device=dev)
+    check(LIB.egz_jpeg_roundtrip(src.data_ptr(), N, H, W, quality, pl.data_ptr() if pl is not None else None,
+                                 out.data_ptr(), out.numel() // (H * W), status.data_ptr(), _stream()),
+          "egz_jpeg_roundtrip")
+    return out, status

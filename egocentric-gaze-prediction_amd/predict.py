@@ -12,7 +12,8 @@ Frames and flows.  With F frames indexed 0 .. F - 1, flow i goes from frame i to
 gets a prediction iff 9 <= k <= F - 2: its flow stack is STdatas.build_temporal_list's -- channel 2m the x-flow k - m, channel
 2m + 1 the y-flow k - m, m = 0 .. 9.  F < 11 is refused.  Every flow is computed once: a chunk hands its last frame (BGR and grey)
 and its last nine flow pairs to the next.  With ``--flow_jpeg Q`` (default 95, extract_flow's) the flow images go through
-jpeg_encode(Q) / jpeg_decode, so that the temporal stream sees the bytes it was trained on; 0 skips that.
+hipops.jpeg_roundtrip(Q) -- the planes jpeg_decode gives for jpeg_encode(Q)'s files, bit for bit, without the bitstream -- so
+that the temporal stream sees the bytes it was trained on; 0 skips that.
 
 Per chunk of n <= ``--chunk`` predictable frames (VideoPredictor._launch): the chunk's BGR planes and its n + 9 flow pairs sit in
 one uint8 pool, a host-built (n, 22) plane table (column 21 = -1: no ground truth) drives ONE resident_gather launch, then
@@ -24,12 +25,13 @@ one uint8 pool, a host-built (n, 22) plane table (column 21 = -1: no ground trut
   5 the saccade frames of the chunk (flag != 1), in order, are ONE lstmnet call at batch 1, state carried across chunks from
     None (AT.extract_late's chain); their outputs replace their rows;
   6 at = weighted_minmax(features_s, rows); fused, planes = late_input(q_sp, at): the hand-over extract_late writes and
-    lateDataset reads, on the device; ``--handover_jpeg Q`` sends both planes through jpeg_encode(Q) / jpeg_decode first (for an
-    LF trained from .jpg-named hand-over files);
+    lateDataset reads, on the device; ``--handover_jpeg Q`` sends both planes through jpeg_roundtrip(Q) first (for an LF
+    trained from .jpg-named hand-over files);
   7 fin = late.fusion(fused) (eval mode, as run_spatialstream runs it); com, _, q_fin = u8_center_of_mass(fin).
 One read-back per chunk (com, com_sp and the status words, waited for a chunk later); ``auto`` needs com_sp on the host before
-step 5 and costs a second one.  jpeg_encode reads the lengths of its files back, once per call: with ``--flow_jpeg`` /
-``--handover_jpeg`` / ``--overlay`` / ``--save_maps`` each encode adds that wait.  File writes are host I/O and run a chunk behind.
+step 5 and costs a second one.  ``--flow_jpeg`` / ``--handover_jpeg`` add no wait: the round trip is one launch whose status
+words come back with the chunk's.  jpeg_encode reads the lengths of its files back, once per call: with ``--overlay`` /
+``--save_maps`` each encode adds that wait.  File writes are host I/O and run a chunk behind.
 
 Fixation flags (``--fixsac``).  ``all`` (default): every frame is a fixation -- the reference README's stated assumption for its
 simple test; the LSTM is never loaded or called.  FILE: one float per frame of the video, line k for frame k, dilated as
@@ -244,13 +246,12 @@ class VideoPredictor:
         return time.perf_counter()
 
     def _jpeg_round_trip(self, planes, quality):
-        """(N, H, W) uint8 -> the same planes after jpeg_encode(quality) and jpeg_decode."""
+        """(N, H, W) uint8 -> the planes jpeg_decode gives for jpeg_encode(quality)'s files, bit for bit, without the files:
+        one jpeg_roundtrip launch, no read-back of file lengths (profiles/flow_handover.txt has the comparison)."""
         from . import hipops as H
-        N, Hh, Ww = planes.shape
-        data, offsets, status = H.jpeg_encode(planes, quality=quality)
-        dec, dstatus = H.jpeg_decode(data, offsets, (Hh, Ww), [1] * N, n3=0)
-        self._codec.append((status, dstatus))
-        return dec.view(N, Hh, Ww)
+        dec, status = H.jpeg_roundtrip(planes.contiguous(), quality)
+        self._codec.append((status, None))
+        return dec
 
     # ---- one chunk, queued
     def _launch(self, plan, files, state, flags_file):

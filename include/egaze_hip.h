@@ -471,6 +471,16 @@ int egz_jpeg_encode(const unsigned char* images, int N, int H, int W, int C, int
 int egz_jpeg_encode_write(const void* ws, size_t ws_bytes, int N, int H, int W, int C, unsigned char* out, long out_bytes,
                           const long* slot_off, const long* slot_cap, long* lengths, int* status, hipStream_t stream);
 
+/* The planes jpeg_decode gives for jpeg_encode's files, without the files (csrc/jpeg_roundtrip.hip): src is N grey planes of
+ * H x W uint8, quality 1 .. 100, 1 <= H, W <= 4096, any N >= 1.  Per 8x8 block: FDCT, quantisation by the table
+ * jpge::setup builds for that quality, dequantisation, IDCT, range limit -- bit-identical with egz_jpeg_encode followed by
+ * egz_jpeg_decode, whose entropy coding is lossless.  Plane i is written to plane planes[i] of dst (dst_planes planes of
+ * H x W; planes null: i).  status[i]: 0 ok, 1 planes[i] outside [0, dst_planes) -- nothing of that plane is written.  A
+ * destination plane may be its own source plane (in place); any other overlap of src with a written plane is undefined.
+ * One launch, no workspace, no host synchronisation. */
+int egz_jpeg_roundtrip(const unsigned char* src, long N, int H, int W, int quality, const long* planes, unsigned char* dst,
+                       long dst_planes, int* status, hipStream_t stream);
+
 /* torch.cat((f, g), dim=1) of two one-channel maps, the late-fusion stack's input (models/late_fusion.py:19):
  * f, g [B][1][H][W] -> out [B][2][H][W]; 16-byte copies when HW % 4 == 0 and the pointers are 16-byte aligned, 4-byte ones otherwise. */
 int egz_cat2_planes(const float* f, const float* g, float* out, int B, long HW, hipStream_t stream);
