@@ -4,6 +4,7 @@ the extraction of the late-fusion training data with the SP model + a forward ho
 Quirks reproduced, not fixed: the prediction made from sample i-1 is scored against
 tanh(target_i) (off-by-one), the loss also crosses video boundaries, and ``prevt`` is never updated so the train
 checkpoint is rewritten whenever the epoch loss is below 999."""
+import functools
 import itertools
 import math
 import os
@@ -309,15 +310,14 @@ class AT():
         self.optimizer_lstm = FusedAdam(self.lstm.parameters(), lr=1e-4)
         if handover_sets is not None:
             from .extractLSTMw import extract_LSTM_training_data
-            budget = int(0.8 * torch.cuda.mem_get_info(self.device)[0]) if resident_gb is None else \
-                int(resident_gb * 1e9) - sum(d.needed_bytes for d in (traindata, valdata))
-            if sum(d.needed_bytes for d in handover_sets) > budget:
-                raise RuntimeError(f"lstm_handover: the LSTM vectors need {sum(d.needed_bytes for d in handover_sets)} bytes, "
-                                   f"{budget} bytes are left of the budget beside the resident dataset: raise "
-                                   f"--gpu_resident_gb or run without --lstm_handover")
-            for d in handover_sets:             # both pools before the extraction starts: a pool that does not fit refuses here
-                d.allocate(self.device, budget)
-                budget -= d.needed_bytes
+            from .data.resident import resident_budget, under_budget
+            # both pools before the extraction starts: a pool that does not fit refuses here
+            under_budget(handover_sets,
+                         resident_budget(self.device, resident_gb, sum(d.needed_bytes for d in (traindata, valdata))),
+                         lambda needed, budget: f"lstm_handover: the LSTM vectors need {needed} bytes, {budget} bytes are left "
+                                                f"of the budget beside the resident dataset: raise --gpu_resident_gb or run "
+                                                f"without --lstm_handover",
+                         lambda d, left: d.allocate(self.device, left))
             extract_LSTM_training_data(save_path=None, trained_model=pretrained_model, device=device, crop_size=crop_size,
                                        traindata=traindata, valdata=valdata, align=align, into=handover_sets,
                                        chunk=lstm_handover_chunk)
@@ -349,6 +349,7 @@ class AT():
         self.lstmValLoader = DataLoader(dataset=lstmDataset(os.path.join(lstm_data_path, 'test'), task),
                                         batch_size=1, shuffle=False, num_workers=0)
         if resident:                           # (after extract_lstm and its barrier: the folders are complete)
+            # (not under_budget's shape: a folder's size is known only once its fill has read the first file)
             for loader in (self.lstmTrainLoader, self.lstmValLoader):
                 loader.dataset.fill(self.device, resident_gb)
                 if resident_gb is not None:    # one budget for both pools
@@ -530,18 +531,10 @@ class AT():
     def _check_into(self, st_set, into):
         """extract_late(into=...)'s preconditions, checked before any launch -> the ResidentSTDataset."""
         from .data.late_resident import ResidentLateDataset
-        from .data.resident import ResidentSTDataset
+        from .data.resident import check_st_source
         who = "extract_late(into=)"
-        if not isinstance(st_set, ResidentSTDataset):
-            raise ValueError(f"{who}: st_loader.dataset must be a ResidentSTDataset (--gpu_resident), got "
-                             f"{type(st_set).__name__}: the frames are taken from its pool on the device")
-        if st_set.pool is None:
-            raise ValueError(f"{who}: the ResidentSTDataset has not been filled (fill(device))")
-        if st_set.pool.device != self.device:
-            raise ValueError(f"{who}: the ST pool is on {st_set.pool.device}, the AT stage runs on {self.device}")
-        missing = [f for f in ('image', 'flow', 'gt') if f not in (st_set._plan or ())]
-        if missing:
-            raise ValueError(f"{who}: field(s) {missing} were not in gpu_fields when the ST pool was filled")
+        check_st_source(st_set, self.device, who, ('image', 'flow', 'gt'), "st_loader", "AT stage",
+                        "the frames are taken from its pool on the device")
         if not (isinstance(into, ResidentLateDataset) and into._handover):
             raise ValueError(f"{who}: into must be a ResidentLateDataset.from_st set")
         if into.pool is None or into.pool.device != self.device:
@@ -791,11 +784,10 @@ class AT():
                 H.late_store(ch.sp.reshape(n, *ch.sp.shape[-2:]), feats.contiguous(), into.pool, rows[k0:k1], gt_pool=st_set.pool,
                              gt_src=st_set.table[k0:k1, 21].contiguous(), status_to=status)
                 mark("late_store", t0)
-                pending.append((k0, status))
-            for k0, status in pending:                                # the one place that waits for the device
-                H.check_resident_status(status['_resident_status'])
-                H.check_late_store_status(H.late_store_status(status['_late_store_status']),
-                                          who=f"extract_late(into=): frames {k0} .. {min(k0 + cap, N) - 1}")
+                pending.append((f"extract_late(into=): frames {k0} .. {k1 - 1}", status))
+            # the one place that waits for the device (the warning of a clamped map points here)
+            H.drain_status(pending, '_late_store_status', H.late_store_status,
+                           functools.partial(H.check_late_store_status, stacklevel=3), H.judge_resident_status)
 
         if into is not None:
             # The file path creates one iterator over st_loader, and creating it draws the loader's base seed from torch's

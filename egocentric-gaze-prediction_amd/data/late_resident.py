@@ -15,12 +15,12 @@ import numpy as np
 import torch
 
 from .lateDataset import lateDataset
-from .resident import _size_of, fill_planned
+from .resident import HandoverPool, _size_of, fill_planned
 
 COLS = 3                                    # table columns: SP prediction, AT map, ground truth
 
 
-class ResidentLateDataset(lateDataset):
+class ResidentLateDataset(HandoverPool, lateDataset):
     """``lateDataset`` whose planes live on the device.  ``decode`` selects how ``fill`` decodes ('gpu': hipops.jpeg_decode
     for the files ``sniff`` takes, the host for the rest).  Usage: ``ds.fill(device)`` once, then any DataLoader with
     ``collate_fn=ds.collate_fn`` and ``num_workers=ds.loader_workers``."""
@@ -34,7 +34,6 @@ class ResidentLateDataset(lateDataset):
         self.collate_fn = self._collate
         self.pool = self.table = None       # device tensors after fill()
         self._plan = None
-        self._handover = self._complete = False     # from_st: the pool is written by AT.extract_late(into=...), not decoded
 
     def _files(self, index):
         return (os.path.join(self.imgPath_s, self.listFiles[index]), os.path.join(self.featPath, self.listFeat[index]),
@@ -118,34 +117,16 @@ class ResidentLateDataset(lateDataset):
         ds._plan = ds._handover = True
         return ds
 
-    def allocate(self, device, budget_bytes=None):
-        """The zero-filled pool and the table of a from_st set on ``device``, under fill_planned's budget rule: a pool that
-        does not fit ``budget_bytes`` (None: 0.8 x the free device memory) raises before anything is allocated."""
-        if not self._handover:
-            raise RuntimeError("ResidentLateDataset.allocate: only a from_st set is allocated empty; fill() decodes the files")
-        device = torch.device(device)
-        if budget_bytes is None:
-            budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
-        if self.needed_bytes > budget_bytes:
-            raise RuntimeError(f"ResidentLateDataset.allocate: the late-fusion planes need {self.needed_bytes} bytes "
-                               f"({self.planes} planes of {self.hw[0]} x {self.hw[1]}), {budget_bytes} bytes are allowed: "
-                               f"run without --late_handover (there is no partial cache)")
+    _READS, _WRITER = "decode", "AT.extract_late(into=...)"
+    _OVER_BUDGET = "run without --late_handover (there is no partial cache)"
+
+    def _allocation_needs(self):
+        return (f"the late-fusion planes need {self.needed_bytes} bytes ({self.planes} planes of {self.hw[0]} x "
+                f"{self.hw[1]})")
+
+    def _allocate_empty(self, device):
         self.pool = torch.zeros((self.planes,) + self.hw, dtype=torch.uint8, device=device)
         self.table = self.plane_table.to(device)
-        self._complete = False
-        return self
-
-    def mark_filled(self):
-        """extract_late's last act: every row has been written, batches may be gathered."""
-        if self.pool is None:
-            raise RuntimeError("ResidentLateDataset.mark_filled: allocate(device) has not run")
-        self._complete = True
-        return self
-
-    @property
-    def filled(self):
-        """The pool is on the device and every plane of it has been written (by fill, or by the extraction of a from_st set)."""
-        return self.pool is not None and (not self._handover or self._complete)
 
     # ------------------------------------------------------------------ fill (decode once)
     def fill(self, device, budget_bytes=None, chunk=2048):
@@ -153,9 +134,7 @@ class ResidentLateDataset(lateDataset):
         pool on ``device``; a pool that does not fit ``budget_bytes`` (None: 0.8 x the free device memory) raises before
         anything is allocated; corrupt data warns, an unsupported, unreadable or wrongly sized file raises, both naming the
         file."""
-        if self._handover:
-            raise RuntimeError("ResidentLateDataset.fill: a from_st set has no files to decode (allocate(), then "
-                               "AT.extract_late(into=...))")
+        self._refuse_fill_of_handover()
         if not self._plan:
             self.plan()
         return fill_planned(self, device, budget_bytes, chunk, "ResidentLateDataset.fill", "--late_resident")

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .LSTMdatas import deferred_steps, lstmDataset
+from .resident import HandoverPool, resident_budget
 
 FILL_THREADS = 16                           # file reads of fill() in flight at most
 VECTOR_WIDTH = 512                          # channels of conv5_3: the length of an extracted vector (a from_st set has no file to ask)
@@ -31,7 +32,7 @@ def lstm_plan(listFiles):
     return steps[:, 0].astype(np.int32), steps[:, 1].astype(np.int32), steps[:, 2].astype(np.uint8)
 
 
-class ResidentLSTMDataset(lstmDataset):
+class ResidentLSTMDataset(HandoverPool, lstmDataset):
     """``lstmDataset`` whose vectors can live on the device.  Usage: ``ds.fill(device)`` once; AT._epoch then runs the plan
     (``pool`` (F, W) fp32, ``plan`` = (in_row, tgt_row, reset) on the device, ``n_steps``) instead of iterating the files."""
 
@@ -41,7 +42,6 @@ class ResidentLSTMDataset(lstmDataset):
         self.plan_host = lstm_plan(self.listFiles)
         self.n_steps = len(self.plan_host[0])
         self.needed_bytes = None            # known once the first file gave the vector length
-        self._handover = self._complete = False     # from_st: the pool is written by extractw(into=...), not read from files
 
     # ------------------------------------------------------------------ planned from the ST dataset (no vector file)
     @classmethod
@@ -79,39 +79,22 @@ class ResidentLSTMDataset(lstmDataset):
         ds.width = VECTOR_WIDTH
         ds.st_index = torch.tensor([i for _, i in rows], dtype=torch.int64)
         ds.needed_bytes = len(rows) * ds.width * 4 + 9 * ds.n_steps
-        ds._handover, ds._complete = True, False
+        ds._handover = True
         return ds
 
-    def allocate(self, device, budget_bytes=None):
-        """The zero-filled (F, 512) pool and the plan of a from_st set on ``device``, under fill's budget rule: a set that does
-        not fit ``budget_bytes`` (None: 0.8 x the free device memory) raises before anything is allocated."""
-        if not self._handover:
-            raise RuntimeError("ResidentLSTMDataset.allocate: only a from_st set is allocated empty; fill() reads the files")
-        self.release()
-        device = torch.device(device)
-        F = len(self.listFiles)
-        if F == 0:
-            raise RuntimeError("ResidentLSTMDataset.allocate: no vectors (no second fixation frame passes the task filter)")
-        if budget_bytes is None:
-            budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
-        if self.needed_bytes > budget_bytes:
-            raise RuntimeError(f"ResidentLSTMDataset.allocate: {F} vectors of {self.width} need {self.needed_bytes} bytes, "
-                               f"{budget_bytes} bytes are allowed: raise --gpu_resident_gb or run without --lstm_handover")
-        self.pool = torch.zeros((F, self.width), dtype=torch.float32, device=device)
+    _READS, _WRITER, _RELEASE_FIRST = "read", "extractLSTMw.extractw(into=...)", True
+    _OVER_BUDGET = "raise --gpu_resident_gb or run without --lstm_handover"
+
+    def _refuse_allocation(self, who):
+        if not self.listFiles:
+            raise RuntimeError(f"{who}: no vectors (no second fixation frame passes the task filter)")
+
+    def _allocation_needs(self):
+        return f"{len(self.listFiles)} vectors of {self.width} need {self.needed_bytes} bytes"
+
+    def _allocate_empty(self, device):
+        self.pool = torch.zeros((len(self.listFiles), self.width), dtype=torch.float32, device=device)
         self.plan = tuple(torch.from_numpy(a).to(device) for a in self.plan_host)
-        return self
-
-    def mark_filled(self):
-        """extractw's last act: every row has been written, the steps may be fetched."""
-        if self.pool is None:
-            raise RuntimeError("ResidentLSTMDataset.mark_filled: allocate(device) has not run")
-        self._complete = True
-        return self
-
-    @property
-    def filled(self):
-        """The pool is on the device and every row of it has been written (by fill, or by the extraction of a from_st set)."""
-        return self.pool is not None and (not self._handover or self._complete)
 
     def __getitem__(self, index):
         """lstmDataset's sample.  A from_st set has no files: it serves the same dict from its pool rows (a read-back per
@@ -146,9 +129,7 @@ class ResidentLSTMDataset(lstmDataset):
         bytes, else RuntimeError before anything is allocated.  A file that is not float32, or not of the first file's length,
         raises ValueError naming it; the pool is None after either."""
         from concurrent.futures import ThreadPoolExecutor
-        if self._handover:
-            raise RuntimeError("ResidentLSTMDataset.fill: a from_st set has no files to read (allocate(), then "
-                               "extractLSTMw.extractw(into=...))")
+        self._refuse_fill_of_handover()
         self.release()
         device = torch.device(device)
         F = len(self.listFiles)
@@ -157,7 +138,7 @@ class ResidentLSTMDataset(lstmDataset):
         first = self._read(self.listFiles[0])
         W = first.numel()
         need = F * W * 4 + 9 * self.n_steps
-        allowed = int(budget_gb * 1e9) if budget_gb is not None else int(0.8 * torch.cuda.mem_get_info(device)[0])
+        allowed = resident_budget(device, budget_gb)
         self.needed_bytes = need
         if need > allowed:
             raise RuntimeError(f"ResidentLSTMDataset.fill: {self.Path} ({F} vectors of {W}) needs {need} bytes, {allowed} bytes "

@@ -117,13 +117,102 @@ def fill_pool(files, hw, decode, device, chunk, planes=None):
     return pool
 
 
+# ----------------------------------------------------------------------------- the memory budget of everything resident
+def resident_budget(device, gb=None, spent=0):
+    """The bytes that resident pools may take on ``device``: ``gb`` GB (--gpu_resident_gb) less the ``spent`` bytes of the
+    pools already there, or, without a figure, 0.8 x what is free on the device now."""
+    if gb is not None:
+        return int(gb * 1e9) - spent
+    return int(0.8 * torch.cuda.mem_get_info(torch.device(device))[0])
+
+
+def under_budget(sets, budget, refusal, action):
+    """Several sets under ONE ``budget`` (bytes): their ``needed_bytes`` are summed and a total above the budget raises
+    ``refusal(needed, budget)`` (-> the message) before anything is allocated; then ``action(ds, what is left)`` -- a fill
+    or an allocate -- runs per set, each taking its bytes off.  A set that needs exactly what is left fits."""
+    needed = sum(ds.needed_bytes for ds in sets)
+    if needed > budget:
+        raise RuntimeError(refusal(needed, budget))
+    for ds in sets:
+        action(ds, budget)
+        budget -= ds.needed_bytes
+
+
+class HandoverPool:
+    """The life cycle of a resident dataset whose pool is written on the device by an extraction, not read from files (the
+    ``from_st`` sets): ``from_st`` sets ``_handover``; ``allocate`` creates the empty pool; the extraction writes it and calls
+    ``mark_filled``; ``filled`` is False in between, and the consumers refuse until then.  A set listed from files
+    (``_handover`` False) is refused by ``allocate``, a from_st set by ``fill``.  The class beside it supplies the nouns
+    (``_READS``: what its fill does with files; ``_WRITER``: the extraction call), ``_allocation_needs()`` (-> the "... need
+    N bytes" half of the over-budget message), ``_OVER_BUDGET`` (the advice that ends that message),
+    ``_allocate_empty(device)`` (the zero-filled pool and what lies beside it) and, where it applies, ``_refuse_allocation(who)``
+    (raises for a set with nothing to allocate) and ``_RELEASE_FIRST`` with a ``release()`` (a new pool must not live
+    beside the old one)."""
+    _handover = _complete = False
+    _RELEASE_FIRST = False
+
+    def _refuse_allocation(self, who):
+        pass
+
+    def allocate(self, device, budget_bytes=None):
+        """The zero-filled pool of a from_st set on ``device``: a set that does not fit ``budget_bytes`` (None:
+        resident_budget's 0.8 x the free device memory) raises before anything is allocated."""
+        who = f"{type(self).__name__}.allocate"
+        if not self._handover:
+            raise RuntimeError(f"{who}: only a from_st set is allocated empty; fill() {self._READS}s the files")
+        if self._RELEASE_FIRST:
+            self.release()
+        device = torch.device(device)
+        self._refuse_allocation(who)
+        if budget_bytes is None:
+            budget_bytes = resident_budget(device)
+        if self.needed_bytes > budget_bytes:
+            raise RuntimeError(f"{who}: {self._allocation_needs()}, {budget_bytes} bytes are allowed: {self._OVER_BUDGET}")
+        self._allocate_empty(device)
+        self._complete = False
+        return self
+
+    def mark_filled(self):
+        """The extraction's last act: every row has been written, the set may be read."""
+        if self.pool is None:
+            raise RuntimeError(f"{type(self).__name__}.mark_filled: allocate(device) has not run")
+        self._complete = True
+        return self
+
+    @property
+    def filled(self):
+        """The pool is on the device and all of it has been written (by fill, or by the extraction of a from_st set)."""
+        return self.pool is not None and (not self._handover or self._complete)
+
+    def _refuse_fill_of_handover(self):
+        if self._handover:
+            raise RuntimeError(f"{type(self).__name__}.fill: a from_st set has no files to {self._READS} (allocate(), then "
+                               f"{self._WRITER})")
+
+
+def check_st_source(st_set, dev, who, fields, loader, stage, why):
+    """The ST half of an ``into=`` extraction's preconditions: ``st_set`` is a ResidentSTDataset, filled, on ``dev``, with
+    ``fields`` in its plan.  ``loader`` / ``stage`` / ``why`` are the caller's words for where the set came from, what runs on
+    ``dev`` and what is taken from the pool."""
+    if not isinstance(st_set, ResidentSTDataset):
+        raise ValueError(f"{who}: {loader}.dataset must be a ResidentSTDataset (--gpu_resident), got {type(st_set).__name__}: "
+                         f"{why}")
+    if st_set.pool is None:
+        raise ValueError(f"{who}: the ResidentSTDataset has not been filled (fill(device))")
+    if st_set.pool.device != dev:
+        raise ValueError(f"{who}: the ST pool is on {st_set.pool.device}, the {stage} runs on {dev}")
+    missing = [f for f in fields if f not in (st_set._plan or ())]
+    if missing:
+        raise ValueError(f"{who}: field(s) {missing} were not in gpu_fields when the ST pool was filled")
+
+
 def fill_planned(ds, device, budget_bytes, chunk, who, flag):
     """``fill`` of a planned resident dataset ``ds``: refuses before allocating when ``needed_bytes`` exceeds ``budget_bytes``
     (None: 0.8 x the free device memory; ``who`` / ``flag`` name the caller and its CLI switch in the message), fills the pool
     (fill_pool), puts the table beside it and prints the number of files, the bytes and the seconds once."""
     device = torch.device(device)
     if budget_bytes is None:
-        budget_bytes = int(0.8 * torch.cuda.mem_get_info(device)[0])
+        budget_bytes = resident_budget(device)
     if ds.needed_bytes > budget_bytes:
         raise RuntimeError(f"{who}: the decoded dataset needs {ds.needed_bytes} bytes "
                            f"({ds.planes} planes of {ds.hw[0]} x {ds.hw[1]}), {budget_bytes} bytes are allowed: "
@@ -325,16 +414,10 @@ def fill_all(datasets, device, budget_gb=None, flag="--gpu_resident", flow_from=
         if flow_from is not None:
             ds.flow_from = flow_from
         ds.plan()
-    budget = int(budget_gb * 1e9) if budget_gb is not None else int(0.8 * torch.cuda.mem_get_info(torch.device(device))[0])
-    needed = sum(ds.needed_bytes for ds in datasets)
-    if needed > budget:
-        raise RuntimeError(f"{flag}: the decoded datasets need {needed} bytes, {budget} bytes are allowed: "
-                           f"run without {flag} (there is no partial cache)")
-    for ds in datasets:
-        if flow_from is not None:
-            ds.fill(device, budget_bytes=budget, flow_from=flow_from, run_flows=False)
-        else:
-            ds.fill(device, budget_bytes=budget)
-        budget -= ds.needed_bytes
+    flows = {} if flow_from is None else dict(flow_from=flow_from, run_flows=False)
+    under_budget(datasets, resident_budget(device, budget_gb),
+                 lambda needed, budget: f"{flag}: the decoded datasets need {needed} bytes, {budget} bytes are allowed: "
+                                        f"run without {flag} (there is no partial cache)",
+                 lambda ds, left: ds.fill(device, budget_bytes=left, **flows))
     if flow_from is not None:
         run_flows_into(datasets, device, flow_from)

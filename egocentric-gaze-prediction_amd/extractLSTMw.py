@@ -135,18 +135,10 @@ def _shard_loader(loader, shard):
 def _check_into(st_set, into, dev):
     """extractw(into=...)'s preconditions, checked before any launch."""
     from .data.lstm_resident import ResidentLSTMDataset
-    from .data.resident import ResidentSTDataset
+    from .data.resident import check_st_source
     who = "extractw(into=)"
-    if not isinstance(st_set, ResidentSTDataset):
-        raise ValueError(f"{who}: loader.dataset must be a ResidentSTDataset (--gpu_resident), got {type(st_set).__name__}: "
-                         f"the frames and the ground truth are taken from its pool on the device")
-    if st_set.pool is None:
-        raise ValueError(f"{who}: the ResidentSTDataset has not been filled (fill(device))")
-    if st_set.pool.device != dev:
-        raise ValueError(f"{who}: the ST pool is on {st_set.pool.device}, the extraction runs on {dev}")
-    missing = [f for f in ('image', 'gt') if f not in (st_set._plan or ())]
-    if missing:
-        raise ValueError(f"{who}: field(s) {missing} were not in gpu_fields when the ST pool was filled")
+    check_st_source(st_set, dev, who, ('image', 'gt'), "loader", "extraction",
+                    "the frames and the ground truth are taken from its pool on the device")
     if not (isinstance(into, ResidentLSTMDataset) and into._handover):
         raise ValueError(f"{who}: into must be a ResidentLSTMDataset.from_st set")
     if into.pool is None or into.pool.device != dev:
@@ -177,15 +169,9 @@ def _extract_into(loader, model, crop_size, dev, into, chunk):
             image = H.resident_gather(st_set.pool, st_set.table, index_dev[k0:k1], fields=('image',), status_to=status)[0]
             feat = model(image)                                   # (n,512,14,14)
             H.lstm_store(to_nhwc(feat), st_set.pool, gt_src[k0:k1], into.pool, rows[k0:k1], crop_size, status_to=status)
-            pending.append((k0, k1, status))
-    # The one place that waits for the device, once: every status word was copied to pinned memory on this stream, in order, so
-    # when the last launch's word has landed all of them have.
-    if pending:
-        H.lstm_store_status(pending[-1][2]['_lstm_store_status'])
-    for k0, k1, status in pending:
-        if int(status['_resident_status'][0][0]):
-            H.check_resident_status(status['_resident_status'])
-        H.check_lstm_store_status(int(status['_lstm_store_status'][0][0]), who=f"extractw(into=): vectors {k0} .. {k1 - 1}")
+            pending.append((f"extractw(into=): vectors {k0} .. {k1 - 1}", status))
+    # The one place that waits for the device, once (drain_status: the words were copied on this stream, in order).
+    H.drain_status(pending, '_lstm_store_status', H.lstm_store_status, H.check_lstm_store_status, H.judge_resident_status)
     into.mark_filled()
 
 

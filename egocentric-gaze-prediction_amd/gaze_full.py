@@ -9,6 +9,24 @@ import torch
 from torch.utils.data import DataLoader
 
 
+# The three in-memory hand-overs: (flag, [(flag it needs, why)], why it runs in one process, the flag it implies).  The parser
+# refuses each where a need is missing or WORLD_SIZE is above 1, in this order.
+_POOL = "the frames and the ground truth are taken from the resident pool on the device"
+_HANDOVERS = (
+    ('lstm_handover', (('gpu_resident', _POOL),
+                       ('extract_lstm', "the LSTM vectors exist only in the memory of the run that extracts them"),
+                       ('train_lstm', "the vectors are not written anywhere, only this run's LSTM training can use them")),
+     "a sharded extraction leaves every rank with its own vectors only", 'lstm_resident'),
+    ('late_handover', (('gpu_resident', _POOL),
+                       ('extract_late', "the late-fusion planes exist only in the memory of the run that extracts them"),
+                       ('train_late', "the planes are not written anywhere, only this run's LF training can use them")),
+     "a sharded extraction leaves every rank with its own chunks only", 'late_resident'),
+    ('flow_handover', (('gpu_resident', "the flow images are written into the resident pool on the device"),
+                       ('framePath', "the flow images are computed from the frames (one folder per video, img_%05d.jpg)")),
+     "every rank would compute every flow", None),
+)
+
+
 def build_parser():
     from .streamtrain import _CheckedParser, add_augment_flags
 
@@ -20,52 +38,27 @@ def build_parser():
             ns, rest = super().parse_known_args(args, namespace)
             if getattr(ns, 'lstm_handover_chunk', None) is not None and not getattr(ns, 'lstm_handover', False):
                 self.error("--lstm_handover_chunk needs --lstm_handover")
-            if getattr(ns, 'lstm_handover', False):
-                if not getattr(ns, 'gpu_resident', False):
-                    self.error("--lstm_handover needs --gpu_resident: the frames and the ground truth are taken from the "
-                               "resident pool on the device")
-                if not ns.extract_lstm:
-                    self.error("--lstm_handover needs --extract_lstm: the LSTM vectors exist only in the memory of the run "
-                               "that extracts them")
-                if not ns.train_lstm:
-                    self.error("--lstm_handover needs --train_lstm: the vectors are not written anywhere, only this run's "
-                               "LSTM training can use them")
-                if ns.align:
+            world = os.environ.get('WORLD_SIZE', '1')
+            for flag, needs, alone, implies in _HANDOVERS:
+                if not getattr(ns, flag, False):
+                    continue
+                for need, why in needs:
+                    if getattr(ns, need, None) in (None, False):
+                        self.error(f"--{flag} needs --{need}: {why}")
+                # (the two checks of --lstm_handover's own extras sit inside the loop only to keep the order of its refusals)
+                if flag == 'lstm_handover' and ns.align:
                     self.error("--lstm_handover does not take --align: the aligned window is built on the host from the "
                                "full-resolution ground truth")
-                if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-                    self.error("--lstm_handover runs in one process: a sharded extraction leaves every rank with its own "
-                               "vectors only (WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
-                if getattr(ns, 'lstm_handover_chunk', 1) < 1:
+                if int(world) > 1:
+                    self.error(f"--{flag} runs in one process: {alone} (WORLD_SIZE is {world})")
+                if flag == 'lstm_handover' and getattr(ns, 'lstm_handover_chunk', 1) < 1:
                     self.error("--lstm_handover_chunk must be at least 1")
-                ns.lstm_resident = True
-            if getattr(ns, 'late_handover', False):
-                if not getattr(ns, 'gpu_resident', False):
-                    self.error("--late_handover needs --gpu_resident: the frames and the ground truth are taken from the "
-                               "resident pool on the device")
-                if not ns.extract_late:
-                    self.error("--late_handover needs --extract_late: the late-fusion planes exist only in the memory of the "
-                               "run that extracts them")
-                if not ns.train_late:
-                    self.error("--late_handover needs --train_late: the planes are not written anywhere, only this run's LF "
-                               "training can use them")
-                if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-                    self.error("--late_handover runs in one process: a sharded extraction leaves every rank with its own "
-                               "chunks only (WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
-                ns.late_resident = True
+                if implies is not None:
+                    setattr(ns, implies, True)
             for flag in ('framePath', 'flow_quality', 'flow_bound'):
                 if getattr(ns, flag, None) is not None and not getattr(ns, 'flow_handover', False):
                     self.error(f"--{flag} needs --flow_handover")
             if getattr(ns, 'flow_handover', False):
-                if not getattr(ns, 'gpu_resident', False):
-                    self.error("--flow_handover needs --gpu_resident: the flow images are written into the resident pool on "
-                               "the device")
-                if getattr(ns, 'framePath', None) is None:
-                    self.error("--flow_handover needs --framePath: the flow images are computed from the frames "
-                               "(one folder per video, img_%05d.jpg)")
-                if int(os.environ.get('WORLD_SIZE', '1')) > 1:
-                    self.error("--flow_handover runs in one process: every rank would compute every flow "
-                               "(WORLD_SIZE is %s)" % os.environ['WORLD_SIZE'])
                 if not 0 <= getattr(ns, 'flow_quality', 95) <= 100:
                     self.error("--flow_quality must be 0 .. 100 (0: no JPEG round trip)")
                 if not getattr(ns, 'flow_bound', 20.0) > 0:
@@ -172,17 +165,13 @@ def _at_stage(args, STTrainData, STValData):
         # starts: a pool that does not fit refuses here, not after the first pass
         from .data.late_resident import ResidentLateDataset
         late = [ResidentLateDataset.from_st(data, task=args.task) for data in (STTrainData, STValData)]
-        gb = getattr(args, 'gpu_resident_gb', None)
-        budget = None if gb is None else int(gb * 1e9) - sum(d.needed_bytes for d in (STTrainData, STValData))
-        if budget is None:
-            budget = int(0.8 * torch.cuda.mem_get_info(att.device)[0])
-        if sum(d.needed_bytes for d in late) > budget:
-            raise RuntimeError(f"--late_handover: the late-fusion planes need {sum(d.needed_bytes for d in late)} bytes, "
-                               f"{budget} bytes are left of the budget beside the resident dataset: run without "
-                               f"--late_handover (there is no partial cache)")
-        for d in late:
-            d.allocate(att.device, budget)
-            budget -= d.needed_bytes
+        from .data.resident import resident_budget, under_budget
+        under_budget(late, resident_budget(att.device, getattr(args, 'gpu_resident_gb', None),
+                                           sum(d.needed_bytes for d in (STTrainData, STValData))),
+                     lambda needed, budget: f"--late_handover: the late-fusion planes need {needed} bytes, {budget} bytes are "
+                                            f"left of the budget beside the resident dataset: run without --late_handover "
+                                            f"(there is no partial cache)",
+                     lambda d, left: d.allocate(att.device, left))
         if not args.train_lstm:
             att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data, into in ((STValData, late[1]), (STTrainData, late[0])):

@@ -92,8 +92,8 @@ REBINDABLE = ("PRECISION", "GRAD_SPLIT", "BWD_PRODUCTS", "_SPLIT_MAX_BYTES", "SP
 
 from .._lib import LIB as _RAW_LIB, check  # noqa: E402,F401
 from ._core import (  # noqa: E402,F401
-    EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_STATS, LIB, PROF, _LibProxy, _Profiler, _WS, _out, _p, _ptr_table, _raw_stream,
-    _req, _stream, workspace,
+    EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_STATS, LIB, LaunchStatus, PROF, _LibProxy, _Profiler, _WS, _out, _p, _ptr_table,
+    _raw_stream, _req, _stream, drain_status, finish_launch, workspace,
 )
 from .packing import (  # noqa: E402,F401
     _BATCH_PINNED, _BATCH_TABLES, _CAPTURE_LOG, _PACKED, _PACK_FN, _UID, _USED, _WEIGHT_EPOCH, _drop_packed, _tag, _uid,
@@ -134,7 +134,7 @@ from .lstm import (  # noqa: E402,F401
 from .metrics import _GAUSS_W, _gauss_weights, aae_auc  # noqa: E402,F401
 from .dataprep import (  # noqa: E402,F401
     AFFINE_STATUS, AugSpec, RESIDENT_STATUS, _AREA_T, _NORM_CONST, _RESIDENT_FIELDS, _area_tables, area_table, bilinear_up,
-    check_resident_status, crop_mean, gaze_gt_maps, late_gather, pixel_weighted_sum, resident_gather,
+    check_resident_status, crop_mean, gaze_gt_maps, judge_resident_status, late_gather, pixel_weighted_sum, resident_gather,
     resident_gather_aug, u8_center_of_mass, u8_normalize, weighted_minmax, window_mean,
 )
 from .jpeg import (  # noqa: E402,F401
@@ -152,5 +152,5 @@ from .flow import (  # noqa: E402,F401
 )
 from .handover import (  # noqa: E402,F401
     LATE_INPUT_STATUS, LATE_STORE_STATUS, LSTM_STORE_STATUS, _map_dev, check_late_store_status, check_lstm_store_status,
-    draw_ring, late_input, late_input_status, late_store, late_store_status, lstm_store, lstm_store_status,
+    check_rows, draw_ring, late_input, late_input_status, late_store, late_store_status, lstm_store, lstm_store_status,
 )

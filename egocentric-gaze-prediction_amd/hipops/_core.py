@@ -1,8 +1,9 @@
-"""What every family shares: the profiler, the one library proxy, stream / pointer helpers, the workspace."""
+"""What every family shares: the profiler, the one library proxy, stream / pointer helpers, the workspace, the launch status
+word."""
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -123,3 +124,43 @@ def workspace(nbytes: int, device) -> torch.Tensor:
 def _ptr_table(tensors):
     """Host array of device pointers (None -> NULL) for the C-ABI entry points that take a parameter table."""
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+# ----------------------------------------------------------------------------- the launch status word
+class LaunchStatus(NamedTuple):
+    """The status word of one launch on its way to the host: ``host`` a one-word pinned tensor the device word is being
+    copied into, ``event`` recorded behind that copy.  A plain tuple to its readers: ``host, event = pending``."""
+    host: torch.Tensor
+    event: object
+
+    def wait(self) -> int:
+        """Waits for the launch -> its status word."""
+        self.event.synchronize()
+        return int(self.host[0])
+
+
+def finish_launch(status: torch.Tensor, status_to: Optional[dict], key: str, judge) -> None:
+    """The tail of every op that ends in a status word: the device word ``status`` is copied to pinned memory behind the
+    launch (non-blocking) and an event recorded.  With ``status_to`` (a dict) the LaunchStatus is left there under ``key``
+    for the caller to wait on later; without, this waits and hands the word to ``judge`` (int -> None: raises or warns)."""
+    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+    host.copy_(status, non_blocking=True)
+    done = torch.cuda.Event()
+    done.record()
+    if status_to is not None:
+        status_to[key] = LaunchStatus(host, done)
+    else:
+        judge(LaunchStatus(host, done).wait())
+
+
+def drain_status(chunks, key: str, wait, judge, judge_resident) -> None:
+    """Judges the status words of ``chunks`` = [(who, status_to dict)], every dict holding the word of a gather
+    ('_resident_status') and of a store (``key``), all queued on ONE stream in this order.  The words were copied on that
+    stream in order, so when the last one has landed all have: ``wait`` (the store's ``*_status`` function) is called once,
+    on the last word, and the rest are read as they lie.  Per chunk ``judge_resident(word)`` comes before
+    ``judge(word, who)``; ``who`` names the chunk in the store's errors."""
+    if chunks:
+        wait(chunks[-1][1][key])
+    for who, status in chunks:
+        judge_resident(int(LaunchStatus(*status['_resident_status']).host[0]))      # (a plain pair will do, as everywhere)
+        judge(int(LaunchStatus(*status[key]).host[0]), who)

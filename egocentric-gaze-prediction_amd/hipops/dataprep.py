@@ -10,7 +10,7 @@ from typing import Optional
 import torch
 
 from .._lib import check
-from ._core import LIB, _p, _req, _stream
+from ._core import LIB, LaunchStatus, _p, _req, _stream, finish_launch
 from .absmax import _new_absmax, _want_fwd_absmax
 from .metrics import _gauss_weights
 
@@ -133,14 +133,16 @@ RESIDENT_STATUS = {1: "a sample number (idx) outside the table", 2: "a plane-tab
 _RESIDENT_FIELDS = {'image': 1, 'flow': 2, 'gt': 4}
 
 
-def check_resident_status(pending) -> None:
-    """Waits for the gather that ``pending = (host status word, event)`` belongs to and raises if it skipped a sample."""
-    host, ev = pending
-    ev.synchronize()
-    st = int(host[0])
+def judge_resident_status(st: int) -> None:
+    """The rule for the status word of a gather (resident_gather, resident_gather_aug, late_gather): any bit raises."""
     if st:
         what = RESIDENT_STATUS.get(st) or AFFINE_STATUS.get(st, st)
         raise RuntimeError(f"resident_gather: {what}: the sample was skipped, its outputs are undefined")
+
+
+def check_resident_status(pending) -> None:
+    """Waits for the gather that ``pending = (host status word, event)`` belongs to and raises if it skipped a sample."""
+    judge_resident_status(LaunchStatus(*pending).wait())
 
 
 def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, fields=('image', 'flow', 'gt'),
@@ -198,14 +200,7 @@ def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, 
         ev = torch.cuda.Event()
         ev.record()
         flow._egz_prepared = (xin, flow._version, ev)
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    done = torch.cuda.Event()
-    done.record()
-    if status_to is not None:
-        status_to['_resident_status'] = (host, done)
-    else:
-        _H.check_resident_status((host, done))
+    finish_launch(status, status_to, '_resident_status', judge_resident_status)
     return out_raw if raw else (image, flow, gt)
 
 
@@ -389,14 +384,7 @@ def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tens
         ev = torch.cuda.Event()
         ev.record()
         flow._egz_prepared = (xin, flow._version, ev)
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    done = torch.cuda.Event()
-    done.record()
-    if status_to is not None:
-        status_to['_resident_status'] = (host, done)
-    else:
-        _H.check_resident_status((host, done))
+    finish_launch(status, status_to, '_resident_status', judge_resident_status)
     out = out_raw if raw else (image, flow, gt)
     return (out, used) if want_params else out
 
@@ -430,14 +418,7 @@ def late_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, raw:
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     check(LIB.egz_late_gather(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W, _p(fused),
                               _p(gt), _p(out_raw), status.data_ptr(), _stream()), "egz_late_gather")
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    done = torch.cuda.Event()
-    done.record()
-    if status_to is not None:
-        status_to['_resident_status'] = (host, done)
-    else:
-        _H.check_resident_status((host, done))
+    finish_launch(status, status_to, '_resident_status', judge_resident_status)
     return out_raw if raw else (fused, gt)
 
 

@@ -3,13 +3,14 @@ resident late-fusion pool), the SP -> AT hand-over (lstm_store: extractLSTMw.ext
 LSTM vector pool) and the gaze marker of an overlay (draw_ring)."""
 from __future__ import annotations
 
+import functools
 import sys
 from typing import Optional
 
 import torch
 
 from .._lib import check
-from ._core import LIB, _p, _stream
+from ._core import LIB, LaunchStatus, _p, _stream, finish_launch
 
 _H = sys.modules[__package__]      # the package: switches and public functions are read through it at call time
 
@@ -17,20 +18,75 @@ LATE_INPUT_STATUS = {1: "a NaN was quantised to 0", 2: "a value outside [0, 1] w
                      3: "a NaN was quantised to 0 and a value outside [0, 1] was clamped"}
 
 
-def _map_dev(t, name, what):
+# ----------------------------------------------------------------------------- the operand checks of the three ops
+def _operand(t, name, what, dtypes, dim, form, dev=None, on="", shape=None, refuse=None):
+    """One device operand of a hand-over op: a tensor on ``dev`` (None: on any GPU), non-empty, of one of ``dtypes`` with
+    ``dim`` dimensions (of exactly ``shape`` where given; ``form`` spells the shape in the message), not refused by
+    ``refuse(t)`` (-> the rest of a message, or None) and contiguous.  ``on`` is the op's wording of "must be ... ``dev``".
+    -> t"""
     if not isinstance(t, torch.Tensor):
         raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if not t.is_cuda:
+    if dev is None and not t.is_cuda:
         raise ValueError(f"{what}: {name} must be a HIP ('cuda') tensor -- this package has no CPU path")
-    if t.dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"{what}: {name} must be float32 or uint8, got {t.dtype}")
-    if t.dim() != 3 or min(t.shape) == 0:
-        raise ValueError(f"{what}: {name} must be a non-empty (B, H, W), got {tuple(t.shape)}")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{what}: {name} must be {on} {dev}, got {t.device}")
+    if t.dtype not in dtypes or t.dim() != dim or min(t.shape) == 0 or (shape is not None and tuple(t.shape) != shape):
+        kinds = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise ValueError(f"{what}: {name} must be a non-empty {kinds} {form}, got {t.dtype} {tuple(t.shape)}")
+    why = refuse(t) if refuse is not None else None
+    if why is not None:
+        raise ValueError(f"{what}: {name} {why}")
     if not t.is_contiguous():
         raise ValueError(f"{what}: {name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
     return t
 
 
+def _map_dev(t, name, what):
+    return _operand(t, name, what, (torch.float32, torch.uint8), 3, "(B, H, W)")
+
+
+def _map_pair(sp, at, what):
+    """The SP and AT maps of late_input / late_store -> (samples, H, W, h, w)."""
+    _map_dev(sp, "sp", what)
+    _map_dev(at, "at", what)
+    if sp.device != at.device:
+        raise ValueError(f"{what}: sp and at must be on one device ({sp.device} vs {at.device})")
+    if sp.shape[0] != at.shape[0]:
+        raise ValueError(f"{what}: {sp.shape[0]} SP maps but {at.shape[0]} AT maps")
+    if sp.shape[0] > 65535:
+        raise ValueError(f"{what}: {sp.shape[0]} samples in one launch (65535 at most)")
+    return tuple(int(v) for v in sp.shape) + (int(at.shape[1]), int(at.shape[2]))
+
+
+def check_rows(dst, shape, dev, what, noun, cols=None):
+    """The host half of _rows_dev: ``dst`` is a contiguous int64 tensor of ``shape`` on ``dev`` or on the host, and outside
+    -1 no number is named twice in it (in its columns ``cols`` where given: the others are not written through).  Two
+    writers of one ``noun`` ('plane', 'row') have no defined order, so a repeat is refused, naming the first.  A device
+    ``dst`` is read back for this (a wait)."""
+    if not (isinstance(dst, torch.Tensor) and dst.dtype == torch.int64 and tuple(dst.shape) == tuple(shape)
+            and dst.is_contiguous() and (dst.device == dev or dst.device.type == 'cpu')):
+        got = f"{dst.dtype} {tuple(dst.shape)} on {dst.device}" if isinstance(dst, torch.Tensor) else type(dst).__name__
+        raise ValueError(f"{what}: dst must be a contiguous int64 {tuple(shape)} tensor on {dev} or on the host, got {got}")
+    named = (dst if cols is None else dst[:, :cols]).cpu().numpy().ravel()
+    named = named[named != -1].tolist()
+    if len(set(named)) != len(named):
+        seen = set()
+        twice = next(int(v) for v in named if v in seen or seen.add(v))
+        raise ValueError(f"{what}: dst names {noun} {twice} twice in one call")
+
+
+def _rows_dev(dst, shape, dev, what, noun, cols=None):
+    """The destination numbers of a store, checked (check_rows) -> on ``dev``: a host ``dst`` is uploaded from pinned memory
+    without waiting for the device."""
+    check_rows(dst, shape, dev, what, noun, cols)
+    if dst.device.type == 'cpu':
+        pinned = torch.empty(tuple(shape), dtype=torch.int64, pin_memory=True)
+        pinned.copy_(dst)
+        dst = pinned.to(dev, non_blocking=True)
+    return dst
+
+
+# ----------------------------------------------------------------------------- AT -> LF
 def late_input(sp: torch.Tensor, at: torch.Tensor, want_u8: bool = False, status_to: Optional[dict] = None):
     """late_fusion's input from the SP map and the AT map of a batch, as AT.extract_late's files and data.lateDataset would
     hand it over, in one launch (egz_late_input).
@@ -44,16 +100,7 @@ def late_input(sp: torch.Tensor, at: torch.Tensor, want_u8: bool = False, status
     of range) is handled as late_gather's: read here (a wait for this launch; a non-zero word warns, the outputs are defined), or,
     with ``status_to`` (a dict), left there as ``(pinned host word, event)`` under '_late_input_status' for late_input_status."""
     what = "late_input"
-    _map_dev(sp, "sp", what)
-    _map_dev(at, "at", what)
-    if sp.device != at.device:
-        raise ValueError(f"{what}: sp and at must be on one device ({sp.device} vs {at.device})")
-    if sp.shape[0] != at.shape[0]:
-        raise ValueError(f"{what}: {sp.shape[0]} SP maps but {at.shape[0]} AT maps")
-    B, Hh, Ww = (int(v) for v in sp.shape)
-    h, w = int(at.shape[1]), int(at.shape[2])
-    if B > 65535:
-        raise ValueError(f"{what}: {B} samples in one launch (65535 at most)")
+    B, Hh, Ww, h, w = _map_pair(sp, at, what)
     if B * 2 * Hh * Ww * 4 >= 1 << 32:
         raise ValueError(f"{what}: a fused output of {B * 2 * Hh * Ww * 4} bytes; below 4 GiB per launch")
     dev = sp.device
@@ -64,43 +111,18 @@ def late_input(sp: torch.Tensor, at: torch.Tensor, want_u8: bool = False, status
     check(LIB.egz_late_input(sp.data_ptr(), int(sp.dtype == torch.uint8), at.data_ptr(), int(at.dtype == torch.uint8), B, Hh, Ww,
                              h, w, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]), fused.data_ptr(), _p(planes),
                              status.data_ptr(), _stream()), "egz_late_input")
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    done = torch.cuda.Event()
-    done.record()
-    if status_to is not None:
-        status_to['_late_input_status'] = (host, done)
-    else:
-        st = _H.late_input_status((host, done))
-        if st:
-            import warnings
-            warnings.warn(f"late_input: {LATE_INPUT_STATUS.get(st, st)}", RuntimeWarning, stacklevel=2)
+    # (bit 2 cannot come up here, so the rule is late_store's; the warning points at this function's caller)
+    finish_launch(status, status_to, '_late_input_status', functools.partial(_H.check_late_store_status, who=what, stacklevel=4))
     return (fused, planes) if want_u8 else fused
 
 
 def late_input_status(pending) -> int:
     """Waits for the late_input launch that ``pending = (host status word, event)`` belongs to -> its status word (0: every
     value was inside [0, 1]; LATE_INPUT_STATUS names the bits).  Nothing was skipped: the outputs are defined either way."""
-    host, ev = pending
-    ev.synchronize()
-    return int(host[0])
+    return LaunchStatus(*pending).wait()
 
 
 LATE_STORE_STATUS = {**LATE_INPUT_STATUS, 4: "a plane number outside its pool (that sample wrote nothing)"}
-
-
-def _pool_dev(t, name, what, dev, hw):
-    if not isinstance(t, torch.Tensor):
-        raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if not t.is_cuda or t.device != dev:
-        raise ValueError(f"{what}: {name} must be a HIP ('cuda') tensor on the maps' device {dev}, got {t.device}")
-    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[0] == 0:
-        raise ValueError(f"{what}: {name} must be a non-empty uint8 (P, H, W), got {t.dtype} {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{what}: {name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
-    if tuple(t.shape[1:]) != hw:
-        raise ValueError(f"{what}: {name} holds planes of {tuple(t.shape[1:])}, sp has {hw}")
-    return t
 
 
 def late_store(sp: torch.Tensor, at: torch.Tensor, late_pool: torch.Tensor, dst: torch.Tensor,
@@ -119,62 +141,37 @@ def late_store(sp: torch.Tensor, at: torch.Tensor, late_pool: torch.Tensor, dst:
     is read here (a wait; bits 0 / 1 warn, bit 2 raises), or, with ``status_to`` (a dict), left there as ``(pinned host word,
     event)`` under '_late_store_status' for late_store_status.  -> late_pool."""
     what = "late_store"
-    _map_dev(sp, "sp", what)
-    _map_dev(at, "at", what)
-    if sp.device != at.device:
-        raise ValueError(f"{what}: sp and at must be on one device ({sp.device} vs {at.device})")
-    if sp.shape[0] != at.shape[0]:
-        raise ValueError(f"{what}: {sp.shape[0]} SP maps but {at.shape[0]} AT maps")
-    n, Hh, Ww = (int(v) for v in sp.shape)
-    h, w = int(at.shape[1]), int(at.shape[2])
-    if n > 65535:
-        raise ValueError(f"{what}: {n} samples in one launch (65535 at most)")
+    n, Hh, Ww, h, w = _map_pair(sp, at, what)
     dev = sp.device
-    _pool_dev(late_pool, "late_pool", what, dev, (Hh, Ww))
+
+    on = "a HIP ('cuda') tensor on the maps' device"
+
+    def other_planes(t):
+        return None if tuple(t.shape[1:]) == (Hh, Ww) else f"holds planes of {tuple(t.shape[1:])}, sp has {(Hh, Ww)}"
+    _operand(late_pool, "late_pool", what, (torch.uint8,), 3, "(P, H, W)", dev, on, refuse=other_planes)
     if (gt_pool is None) != (gt_src is None):
         raise ValueError(f"{what}: gt_pool and gt_src go together")
     if gt_pool is not None:
-        _pool_dev(gt_pool, "gt_pool", what, dev, (Hh, Ww))
-        if not (isinstance(gt_src, torch.Tensor) and gt_src.device == dev and gt_src.dtype == torch.int64
-                and tuple(gt_src.shape) == (n,) and gt_src.is_contiguous()):
-            raise ValueError(f"{what}: gt_src must be a contiguous int64 ({n},) tensor on {dev}")
+        _operand(gt_pool, "gt_pool", what, (torch.uint8,), 3, "(P, H, W)", dev, on, refuse=other_planes)
+        _operand(gt_src, "gt_src", what, (torch.int64,), 1, f"({n},)", dev, on, shape=(n,))
         lo, hi = late_pool.data_ptr(), late_pool.data_ptr() + late_pool.numel()
         if gt_pool.data_ptr() < hi and lo < gt_pool.data_ptr() + gt_pool.numel():
             raise ValueError(f"{what}: gt_pool overlaps late_pool")
-    if not (isinstance(dst, torch.Tensor) and dst.dtype == torch.int64 and tuple(dst.shape) == (n, 3)
-            and dst.is_contiguous() and (dst.device == dev or dst.device.type == 'cpu')):
-        raise ValueError(f"{what}: dst must be a contiguous int64 ({n}, 3) tensor on {dev} or on the host")
-    named = (dst if gt_pool is not None else dst[:, :2]).cpu().numpy().ravel()      # (a device dst: a wait)
-    named = named[named != -1]
-    if len(set(named.tolist())) != named.size:
-        seen = set()
-        twice = next(int(v) for v in named.tolist() if v in seen or seen.add(v))
-        raise ValueError(f"{what}: dst names plane {twice} twice in one call")
-    if dst.device.type == 'cpu':
-        pinned = torch.empty((n, 3), dtype=torch.int64, pin_memory=True)
-        pinned.copy_(dst)
-        dst = pinned.to(dev, non_blocking=True)
+    dst = _rows_dev(dst, (n, 3), dev, what, "plane", cols=None if gt_pool is not None else 2)
     tabs = (None,) * 4 if (h, w) == (Hh, Ww) else _H._linear_tables(dev, (h, w), (Hh, Ww), what)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     check(LIB.egz_late_store(sp.data_ptr(), int(sp.dtype == torch.uint8), at.data_ptr(), int(at.dtype == torch.uint8), n, Hh, Ww,
                              h, w, _p(tabs[0]), _p(tabs[1]), _p(tabs[2]), _p(tabs[3]), late_pool.data_ptr(),
                              late_pool.shape[0], dst.data_ptr(), _p(gt_pool), 0 if gt_pool is None else gt_pool.shape[0],
                              _p(gt_src), status.data_ptr(), _stream()), "egz_late_store")
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    done = torch.cuda.Event()
-    done.record()
-    if status_to is not None:
-        status_to['_late_store_status'] = (host, done)
-    else:
-        check_late_store_status(_H.late_store_status((host, done)), stacklevel=3)
+    finish_launch(status, status_to, '_late_store_status', functools.partial(_H.check_late_store_status, stacklevel=4))
     return late_pool
 
 
 def late_store_status(pending) -> int:
     """Waits for the late_store launch that ``pending = (host status word, event)`` belongs to -> its status word
     (LATE_STORE_STATUS names the bits)."""
-    return late_input_status(pending)
+    return LaunchStatus(*pending).wait()
 
 
 def check_late_store_status(st: int, who: str = "late_store", stacklevel: int = 2):
@@ -187,6 +184,7 @@ def check_late_store_status(st: int, who: str = "late_store", stacklevel: int = 
         warnings.warn(f"{who}: {LATE_STORE_STATUS.get(st, st)}", RuntimeWarning, stacklevel=stacklevel)
 
 
+# ----------------------------------------------------------------------------- SP -> AT
 LSTM_STORE_STATUS = {1: "a ground-truth plane number or a pool row outside its pool (that sample wrote nothing)"}
 
 
@@ -206,16 +204,12 @@ def lstm_store(feat_nhwc: torch.Tensor, gt_pool: torch.Tensor, gt_src: torch.Ten
     writes nothing and bit 0 of the status word goes up.  The word is read here (a wait; bit 0 raises), or, with ``status_to``
     (a dict), left there as ``(pinned host word, event)`` under '_lstm_store_status' for lstm_store_status.
     -> pool, or (pool, cells) with ``want_cells``: cells int32 (B,), the flat gaze cell of every stored sample (-1: skipped)."""
-    what = "lstm_store"
+    what, on = "lstm_store", "on the features' device"
     for name, t in (("feat_nhwc", feat_nhwc), ("gt_pool", gt_pool), ("gt_src", gt_src), ("pool", pool), ("dst", dst)):
-        if not isinstance(t, torch.Tensor):
+        if not isinstance(t, torch.Tensor):           # all five before anything else is judged
             raise ValueError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
-    if not feat_nhwc.is_cuda:
-        raise ValueError(f"{what}: feat_nhwc must be a HIP ('cuda') tensor -- this package has no CPU path")
+    _operand(feat_nhwc, "feat_nhwc", what, (torch.float32,), 4, "(B, H, W, C)")
     dev = feat_nhwc.device
-    if feat_nhwc.dtype != torch.float32 or feat_nhwc.dim() != 4 or min(feat_nhwc.shape) == 0:
-        raise ValueError(f"{what}: feat_nhwc must be a non-empty float32 (B, H, W, C), got {feat_nhwc.dtype} "
-                         f"{tuple(feat_nhwc.shape)}")
     B, Hh, Ww, C = (int(v) for v in feat_nhwc.shape)
     if Hh != Ww:
         raise ValueError(f"{what}: a {Hh} x {Ww} map: H == W is needed (the reference clips both window coordinates with H)")
@@ -224,56 +218,27 @@ def lstm_store(feat_nhwc: torch.Tensor, gt_pool: torch.Tensor, gt_src: torch.Ten
     for name, v, lo, hi in (("cell", cell, 1, 256), ("size", size, 1, Hh)):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise ValueError(f"{what}: {name} must be an integer in {lo} .. {hi}, got {v!r}")
-    for name, t in (("gt_pool", gt_pool), ("gt_src", gt_src), ("pool", pool)):
-        if t.device != dev:
-            raise ValueError(f"{what}: {name} must be on the features' device {dev}, got {t.device}")
-    if gt_pool.dtype != torch.uint8 or gt_pool.dim() != 3 or gt_pool.shape[0] == 0:
-        raise ValueError(f"{what}: gt_pool must be a non-empty uint8 (Q, H, W), got {gt_pool.dtype} {tuple(gt_pool.shape)}")
-    if tuple(gt_pool.shape[1:]) != (Hh * cell, Ww * cell):
-        raise ValueError(f"{what}: gt_pool holds planes of {tuple(gt_pool.shape[1:])}, a {Hh} x {Ww} map with cell {cell} "
-                         f"needs {(Hh * cell, Ww * cell)}")
-    if pool.dtype != torch.float32 or pool.dim() != 2 or pool.shape[0] == 0:
-        raise ValueError(f"{what}: pool must be a non-empty float32 (rows, C), got {pool.dtype} {tuple(pool.shape)}")
-    if pool.shape[1] != C:
-        raise ValueError(f"{what}: pool rows hold {pool.shape[1]} values, feat_nhwc has C = {C} channels")
-    if gt_src.dtype != torch.int64 or tuple(gt_src.shape) != (B,):
-        raise ValueError(f"{what}: gt_src must be an int64 ({B},) tensor, got {gt_src.dtype} {tuple(gt_src.shape)}")
-    if dst.dtype != torch.int64 or tuple(dst.shape) != (B,) or not (dst.device == dev or dst.device.type == 'cpu'):
-        raise ValueError(f"{what}: dst must be an int64 ({B},) tensor on {dev} or on the host, got {dst.dtype} "
-                         f"{tuple(dst.shape)} on {dst.device}")
-    for name, t in (("feat_nhwc", feat_nhwc), ("gt_pool", gt_pool), ("gt_src", gt_src), ("pool", pool), ("dst", dst)):
-        if not t.is_contiguous():
-            raise ValueError(f"{what}: {name} must be contiguous, got strides {t.stride()} for {tuple(t.shape)}")
-    named = dst.cpu().numpy()                                                     # (a device dst: a wait)
-    named = named[named != -1]
-    if len(set(named.tolist())) != named.size:
-        seen = set()
-        twice = next(int(v) for v in named.tolist() if v in seen or seen.add(v))
-        raise ValueError(f"{what}: dst names row {twice} twice in one call")
-    if dst.device.type == 'cpu':
-        pinned = torch.empty((B,), dtype=torch.int64, pin_memory=True)
-        pinned.copy_(dst)
-        dst = pinned.to(dev, non_blocking=True)
+    planes = (Hh * cell, Ww * cell)
+    _operand(gt_pool, "gt_pool", what, (torch.uint8,), 3, "(Q, H, W)", dev, on,
+             refuse=lambda t: None if tuple(t.shape[1:]) == planes else
+             f"holds planes of {tuple(t.shape[1:])}, a {Hh} x {Ww} map with cell {cell} needs {planes}")
+    _operand(pool, "pool", what, (torch.float32,), 2, "(rows, C)", dev, on,
+             refuse=lambda t: None if t.shape[1] == C else f"rows hold {t.shape[1]} values, feat_nhwc has C = {C} channels")
+    _operand(gt_src, "gt_src", what, (torch.int64,), 1, f"({B},)", dev, on, shape=(B,))
+    dst = _rows_dev(dst, (B,), dev, what, "row")
     cells = torch.full((B,), -1, dtype=torch.int32, device=dev) if want_cells else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     check(LIB.egz_lstm_store(feat_nhwc.data_ptr(), B, Hh, Ww, C, gt_pool.data_ptr(), gt_pool.shape[0], gt_src.data_ptr(), cell,
                              size, pool.data_ptr(), pool.shape[0], dst.data_ptr(), _p(cells), status.data_ptr(), _stream()),
           "egz_lstm_store")
-    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-    host.copy_(status, non_blocking=True)
-    done = torch.cuda.Event()
-    done.record()
-    if status_to is not None:
-        status_to['_lstm_store_status'] = (host, done)
-    else:
-        _H.check_lstm_store_status(_H.lstm_store_status((host, done)))
+    finish_launch(status, status_to, '_lstm_store_status', _H.check_lstm_store_status)
     return (pool, cells) if want_cells else pool
 
 
 def lstm_store_status(pending) -> int:
     """Waits for the lstm_store launch that ``pending = (host status word, event)`` belongs to -> its status word
     (LSTM_STORE_STATUS names the bit)."""
-    return _H.late_input_status(pending)
+    return LaunchStatus(*pending).wait()
 
 
 def check_lstm_store_status(st: int, who: str = "lstm_store"):
