@@ -17,6 +17,12 @@ LIB_PATH = os.environ.get("EGAZE_HIP_LIB") or os.path.join(_HERE, "csrc", "libeg
 P = c_void_p          # device pointer
 S = c_void_p          # hipStream_t
 
+# What the three SP / AT gathers begin with -- pool, P, table, N, idx, B, H, W, mean, std, image, flow, gt, flow_nhwc32, absmax,
+# raw, raw_fields, status -- and the draw's spec of the two with augmentation: seed, epoch, flip_thr, max_shift, contrast,
+# brightness, params_in, params_out.
+_RESIDENT_PREFIX = [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P]
+_AUG_DRAW = [c_uint64, c_uint64, c_uint64, c_int, c_float, c_float, P, P]
+
 # name -> (restype, argtypes).  Must list every symbol include/egaze_hip.h declares
 # (tests/test_cabi_symbols.py cross-checks the header against this table and the .so).
 SIGNATURES = {
@@ -123,11 +129,9 @@ SIGNATURES = {
     # --- optimizer
     "egz_cat2_planes": (c_int, [P, P, P, c_int, c_long, S]),
     "egz_u8_normalize": (c_int, [P, P, c_long, c_long, c_int, P, P, S]),
-    "egz_resident_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P, S]),
-    "egz_resident_gather_aug": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P,
-                                        c_uint64, c_uint64, c_uint64, c_int, c_float, c_float, P, P, S]),
-    "egz_resident_gather_affine": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, P, P, P, P, c_int, P,
-                                           c_uint64, c_uint64, c_uint64, c_int, c_float, c_float, P, P, c_float, c_float, S]),
+    "egz_resident_gather": (c_int, [*_RESIDENT_PREFIX, S]),
+    "egz_resident_gather_aug": (c_int, [*_RESIDENT_PREFIX, *_AUG_DRAW, S]),
+    "egz_resident_gather_affine": (c_int, [*_RESIDENT_PREFIX, *_AUG_DRAW, c_float, c_float, S]),
     "egz_late_gather": (c_int, [P, c_long, P, c_long, P, c_int, c_int, c_int, P, P, P, P, S]),
     "egz_lstm_pool_fetch": (c_int, [P, c_long, c_int, P, P, P, c_long, P, P, P, P, c_long, P, S]),
     "egz_lstm_store": (c_int, [P, c_int, c_int, c_int, c_int, P, c_long, P, c_int, c_int, P, c_long, P, P, P, S]),

@@ -145,6 +145,75 @@ def check_resident_status(pending) -> None:
     judge_resident_status(LaunchStatus(*pending).wait())
 
 
+def _gather_operands(name, pool, table, idx, cols):
+    """The operand checks of the gathers (``name`` the public function, ``cols`` the table's width) -> (device, P, H, W, B)."""
+    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
+            and pool.is_contiguous()):
+        raise ValueError(f"{name}: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
+    dev = pool.device
+    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == cols
+            and table.is_contiguous()):
+        raise ValueError(f"{name}: table must be a contiguous int64 (N, {cols}) tensor on the pool's device")
+    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
+        raise ValueError(f"{name}: idx must be a contiguous int64 (B,) tensor on the pool's device")
+    return (dev, *pool.shape, idx.numel())
+
+
+def _resident_fields(name, fields):
+    fields = tuple(fields)
+    if not fields or any(f not in _RESIDENT_FIELDS for f in fields):
+        raise ValueError(f"{name}: fields {fields!r} must name some of 'image', 'flow', 'gt'")
+    return fields
+
+
+def _resident_consts(dev):
+    """Mean and std of the 24 planes of the SP / AT layout (image 3, flow 20, ground truth 0 / 1) on ``dev``, made once."""
+    from ..data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
+    key = ('resident', dev.index or 0)
+    const = _NORM_CONST.get(key)
+    if const is None:
+        const = (torch.tensor(IMAGE_MEAN + FLOW_MEAN + (0.0,), dtype=torch.float32, device=dev),
+                 torch.tensor(IMAGE_STD + FLOW_STD + (1.0,), dtype=torch.float32, device=dev))
+        _NORM_CONST[key] = const
+    return const
+
+
+def _resident_outputs(dev, B, H, W, fields, raw, prepare):
+    """The outputs of an SP / AT gather -> (image, flow, gt, xin, am, out_raw), None for what the launch does not produce: the
+    bytes alone with ``raw``; the NHWC-32 flow stack and its abs-max buffer under the conditions of prepare_network_input."""
+    new = lambda C: torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    image = flow = gt = xin = am = out_raw = None
+    if raw:
+        out_raw = torch.empty((B, 24, H, W), dtype=torch.uint8, device=dev)
+    else:
+        image = new(3) if 'image' in fields else None
+        flow = new(20) if 'flow' in fields else None
+        gt = new(1) if 'gt' in fields else None
+        if flow is not None and prepare and _H.PRECISION == "split":
+            xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
+            am = _new_absmax(dev)
+    return image, flow, gt, xin, am, out_raw
+
+
+def _resident_args(pool, table, idx, fields, outputs, status):
+    """The 18 arguments the three SP / AT entry points begin with (_lib._RESIDENT_PREFIX)."""
+    mean, std = _resident_consts(pool.device)
+    P, H, W = pool.shape
+    return (pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), idx.numel(), H, W, mean.data_ptr(),
+            std.data_ptr(), *(_p(t) for t in outputs), sum(_RESIDENT_FIELDS[f] for f in set(fields)), status.data_ptr())
+
+
+def _attach_prepared(flow, xin, am):
+    """Lets the NHWC-32 form that came out of the gather's launch ride on ``flow`` (``flow._egz_prepared``)."""
+    if xin is None:
+        return
+    if _want_fwd_absmax():
+        xin._egz_absmax = am
+    ev = torch.cuda.Event()
+    ev.record()
+    flow._egz_prepared = (xin, flow._version, ev)
+
+
 def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, fields=('image', 'flow', 'gt'),
                     raw: bool = False, prepare: bool = True, status_to: Optional[dict] = None):
     """A batch of the SP / AT sample layout gathered from a pool of decoded planes on the device (egz_resident_gather).
@@ -157,49 +226,13 @@ def resident_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, 
     come out of the same launch and ride on ``flow`` (``flow._egz_prepared``).  An index out of range is never dereferenced:
     the status word is read here (a wait for this launch), or, with ``status_to`` (a dict, e.g. the collated sample), left
     there under '_resident_status' for check_resident_status at hand-over."""
-    from ..data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
-    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
-            and pool.is_contiguous()):
-        raise ValueError("resident_gather: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
-    dev = pool.device
-    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 22
-            and table.is_contiguous()):
-        raise ValueError("resident_gather: table must be a contiguous int64 (N, 22) tensor on the pool's device")
-    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
-        raise ValueError("resident_gather: idx must be a contiguous int64 (B,) tensor on the pool's device")
-    fields = tuple(fields)
-    if not fields or any(f not in _RESIDENT_FIELDS for f in fields):
-        raise ValueError(f"resident_gather: fields {fields!r} must name some of 'image', 'flow', 'gt'")
-    P, H, W = pool.shape
-    B = idx.numel()
-    key = ('resident', dev.index or 0)
-    const = _NORM_CONST.get(key)
-    if const is None:
-        const = (torch.tensor(IMAGE_MEAN + FLOW_MEAN + (0.0,), dtype=torch.float32, device=dev),
-                 torch.tensor(IMAGE_STD + FLOW_STD + (1.0,), dtype=torch.float32, device=dev))
-        _NORM_CONST[key] = const
-    new = lambda C: torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-    image = flow = gt = xin = am = out_raw = None
-    if raw:
-        out_raw = torch.empty((B, 24, H, W), dtype=torch.uint8, device=dev)
-    else:
-        image = new(3) if 'image' in fields else None
-        flow = new(20) if 'flow' in fields else None
-        gt = new(1) if 'gt' in fields else None
-        if flow is not None and prepare and _H.PRECISION == "split":
-            xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
-            am = _new_absmax(dev)
+    dev, P, H, W, B = _gather_operands("resident_gather", pool, table, idx, 22)
+    fields = _resident_fields("resident_gather", fields)
+    image, flow, gt, xin, am, out_raw = _resident_outputs(dev, B, H, W, fields, raw, prepare)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    check(LIB.egz_resident_gather(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
-                                  const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin), _p(am),
-                                  _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)), status.data_ptr(), _stream()),
-          "egz_resident_gather")
-    if xin is not None:
-        if _want_fwd_absmax():
-            xin._egz_absmax = am
-        ev = torch.cuda.Event()
-        ev.record()
-        flow._egz_prepared = (xin, flow._version, ev)
+    check(LIB.egz_resident_gather(*_resident_args(pool, table, idx, fields, (image, flow, gt, xin, am, out_raw), status),
+                                  _stream()), "egz_resident_gather")
+    _attach_prepared(flow, xin, am)
     finish_launch(status, status_to, '_resident_status', judge_resident_status)
     return out_raw if raw else (image, flow, gt)
 
@@ -318,26 +351,13 @@ def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tens
     of the angle theta in radians -- goes through egz_resident_gather_affine: the picture is magnified
     and turned about its centre, sampled bilinearly, and the flow vectors turn and scale with it; the parameters used are then
     (B, 7) rows.  Without either the launch and its results are the ones described above."""
-    from ..data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD
     if not isinstance(spec, AugSpec):
         raise ValueError(f"resident_gather_aug: spec must be an AugSpec, got {type(spec).__name__}")
     epoch = int(epoch)
     if not 0 <= epoch < 1 << 64:
         raise ValueError(f"resident_gather_aug: epoch = {epoch} outside 0 .. 2^64 - 1")
-    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
-            and pool.is_contiguous()):
-        raise ValueError("resident_gather_aug: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
-    dev = pool.device
-    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 22
-            and table.is_contiguous()):
-        raise ValueError("resident_gather_aug: table must be a contiguous int64 (N, 22) tensor on the pool's device")
-    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
-        raise ValueError("resident_gather_aug: idx must be a contiguous int64 (B,) tensor on the pool's device")
-    fields = tuple(fields)
-    if not fields or any(f not in _RESIDENT_FIELDS for f in fields):
-        raise ValueError(f"resident_gather_aug: fields {fields!r} must name some of 'image', 'flow', 'gt'")
-    P, H, W = pool.shape
-    B = idx.numel()
+    dev, P, H, W, B = _gather_operands("resident_gather_aug", pool, table, idx, 22)
+    fields = _resident_fields("resident_gather_aug", fields)
     if params is not None and not (isinstance(params, torch.Tensor) and params.device == dev and params.dtype == torch.int32
                                    and tuple(params.shape) in ((B, 5), (B, 7)) and params.is_contiguous()):
         raise ValueError(f"resident_gather_aug: params must be a contiguous int32 ({B}, 5) tensor on the pool's device"
@@ -345,45 +365,16 @@ def resident_gather_aug(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tens
     affine = spec.affine or (params is not None and params.shape[1] == 7)
     if affine and params is not None and params.shape[1] != 7:
         raise ValueError(f"resident_gather_aug: a spec with scale / rotate takes params of ({B}, 7) rows, got ({B}, 5)")
-    key = ('resident', dev.index or 0)
-    const = _NORM_CONST.get(key)
-    if const is None:
-        const = (torch.tensor(IMAGE_MEAN + FLOW_MEAN + (0.0,), dtype=torch.float32, device=dev),
-                 torch.tensor(IMAGE_STD + FLOW_STD + (1.0,), dtype=torch.float32, device=dev))
-        _NORM_CONST[key] = const
-    new = lambda C: torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
-    image = flow = gt = xin = am = out_raw = None
-    if raw:
-        out_raw = torch.empty((B, 24, H, W), dtype=torch.uint8, device=dev)
-    else:
-        image = new(3) if 'image' in fields else None
-        flow = new(20) if 'flow' in fields else None
-        gt = new(1) if 'gt' in fields else None
-        if flow is not None and prepare and _H.PRECISION == "split":
-            xin = torch.empty((B, H, W, 32), dtype=torch.float32, device=dev)
-            am = _new_absmax(dev)
+    image, flow, gt, xin, am, out_raw = _resident_outputs(dev, B, H, W, fields, raw, prepare)
     used = torch.empty((B, 7 if affine else 5), dtype=torch.int32, device=dev) if want_params else None
     status = torch.zeros(1, dtype=torch.int32, device=dev)
+    args = (*_resident_args(pool, table, idx, fields, (image, flow, gt, xin, am, out_raw), status), spec.seed, epoch,
+            spec.flip_thr, spec.shift, spec.contrast, spec.brightness, _p(params), _p(used))
     if affine:
-        check(LIB.egz_resident_gather_affine(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
-                                             const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin),
-                                             _p(am), _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)),
-                                             status.data_ptr(), spec.seed, epoch, spec.flip_thr, spec.shift, spec.contrast,
-                                             spec.brightness, _p(params), _p(used), spec.scale, spec.rotate_rad, _stream()),
-              "egz_resident_gather_affine")
+        check(LIB.egz_resident_gather_affine(*args, spec.scale, spec.rotate_rad, _stream()), "egz_resident_gather_affine")
     else:
-        check(LIB.egz_resident_gather_aug(pool.data_ptr(), P, table.data_ptr(), table.shape[0], idx.data_ptr(), B, H, W,
-                                          const[0].data_ptr(), const[1].data_ptr(), _p(image), _p(flow), _p(gt), _p(xin),
-                                          _p(am), _p(out_raw), sum(_RESIDENT_FIELDS[f] for f in set(fields)),
-                                          status.data_ptr(), spec.seed, epoch, spec.flip_thr, spec.shift, spec.contrast,
-                                          spec.brightness, _p(params), _p(used), _stream()),
-              "egz_resident_gather_aug")
-    if xin is not None:
-        if _want_fwd_absmax():
-            xin._egz_absmax = am
-        ev = torch.cuda.Event()
-        ev.record()
-        flow._egz_prepared = (xin, flow._version, ev)
+        check(LIB.egz_resident_gather_aug(*args, _stream()), "egz_resident_gather_aug")
+    _attach_prepared(flow, xin, am)
     finish_launch(status, status_to, '_resident_status', judge_resident_status)
     out = out_raw if raw else (image, flow, gt)
     return (out, used) if want_params else out
@@ -398,17 +389,7 @@ def late_gather(pool: torch.Tensor, table: torch.Tensor, idx: torch.Tensor, raw:
     (bit-identical); fused channel 0 is the AT map and channel 1 the SP prediction, the tensor late_fusion's Cat2Planes would
     build.  With ``raw=True`` instead the uint8 (B,3,H,W) bytes in table order.  The status word is handled as in
     resident_gather."""
-    if not (isinstance(pool, torch.Tensor) and pool.is_cuda and pool.dtype == torch.uint8 and pool.dim() == 3
-            and pool.is_contiguous()):
-        raise ValueError("late_gather: pool must be a contiguous uint8 (P, H, W) tensor on the GPU")
-    dev = pool.device
-    if not (table.device == dev and table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 3
-            and table.is_contiguous()):
-        raise ValueError("late_gather: table must be a contiguous int64 (N, 3) tensor on the pool's device")
-    if not (idx.device == dev and idx.dtype == torch.int64 and idx.dim() == 1 and idx.is_contiguous()):
-        raise ValueError("late_gather: idx must be a contiguous int64 (B,) tensor on the pool's device")
-    P, H, W = pool.shape
-    B = idx.numel()
+    dev, P, H, W, B = _gather_operands("late_gather", pool, table, idx, 3)
     fused = gt = out_raw = None
     if raw:
         out_raw = torch.empty((B, 3, H, W), dtype=torch.uint8, device=dev)

@@ -195,6 +195,28 @@ def test_offsets_above_4_gib():
     mean, std = _consts()
     cpu = (last.float().div(255) - mean.view(24, 1, 1)) / std.view(24, 1, 1)
     assert torch.equal(torch.cat([image, flow, gt], dim=1).cpu()[0], cpu)
+    # The same pool and table through the gathers with augmentation, whose pixel numbers are 32 bits wide but whose plane offsets
+    # are not: identity rows of 5 words (egz_resident_gather_aug) and of 7 (egz_resident_gather_affine) give the same bytes and
+    # values, a flipped and shifted row gives the restatement applied to the 24 planes.
+    import augment_ref as A
+    one, zero = np.float32(1.0), np.float32(0.0)
+    five = A.rows([A.IDENTITY])
+    seven = np.concatenate([five, np.array([[one, zero]], dtype=np.float32).view(np.int32)], axis=1)
+    for rows in (five, seven):
+        params = torch.from_numpy(rows).to(DEV)
+        raw = Hp.resident_gather_aug(pool, table, idx, Hp.AugSpec(), 0, raw=True, params=params)
+        assert torch.equal(raw.cpu()[0], last), rows.shape
+        image, flow, gt = Hp.resident_gather_aug(pool, table, idx, Hp.AugSpec(), 0, params=params)
+        got = torch.cat([image, flow, gt], dim=1).cpu()[0]
+        assert torch.equal(got.view(torch.int32), cpu.view(torch.int32)), rows.shape
+    moved = [(1, 1, -3, one, zero)]
+    want_raw, want = A.batch(last.numpy()[None], moved, mean.numpy(), std.numpy())
+    params = torch.from_numpy(A.rows(moved)).to(DEV)
+    raw = Hp.resident_gather_aug(pool, table, idx, Hp.AugSpec(), 0, raw=True, params=params)
+    assert torch.equal(raw.cpu(), torch.from_numpy(want_raw))
+    image, flow, gt = Hp.resident_gather_aug(pool, table, idx, Hp.AugSpec(), 0, params=params)
+    got = torch.cat([image, flow, gt], dim=1).cpu()
+    assert torch.equal(got.view(torch.int32), torch.from_numpy(want).view(torch.int32))
     del flat, pool
 
 

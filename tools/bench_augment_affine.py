@@ -90,6 +90,8 @@ def gather(regions, calls, B=32, H=224, W=224):
         emit(f"gather {name:15s} median {ms:.4f} ms  (min {min(ts[name]):.4f}, max {max(ts[name]):.4f})  "
              f"{nbytes / ms / 1e6:6.0f} GB/s  x{ms / base:.3f} of plain"
              + (f"  bit-identical with aug_identity: {bool(same)}" if name == "affine_identity" else ""))
+    for name in variants:
+        emit(f"# regions {name:15s} " + " ".join(f"{v:.4f}" for v in ts[name]))
     return {k: (float(np.median(v)), min(v), max(v)) for k, v in ts.items()}
 
 
