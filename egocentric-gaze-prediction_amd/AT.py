@@ -23,9 +23,9 @@ from .functions import MSELoss
 from .models.LSTMnet import lstmnet
 from .models.model_SP import model_SP
 from .optim import FusedAdam
-from .SP import _progress
-from .utils import (AverageMeter, cfg, computeAAEAUC, generalException, make_layers, owned_state_dict, plot_loss,
-                    repackage_hidden)
+from .trainloop import progress as _progress
+from .utils import (AverageMeter, cfg, computeAAEAUC, generalException, load_merged, make_layers, owned_state_dict,
+                    plot_loss, repackage_hidden)
 
 hook_name = 'features_s'
 features_blobs = []
@@ -332,9 +332,7 @@ class AT():
         self.lstm_save_img, self.save_path, self.save_name = lstm_save_img, save_path, save_name
         self.lstm_data_path, self.batch_size, self.align = lstm_data_path, 1, align
         self.model = model_SP(make_layers(cfg['D'], 3), make_layers(cfg['D'], 20))
-        merged = self.model.state_dict()
-        merged.update(torch.load(pretrained_model, map_location='cpu', weights_only=False)['state_dict'])
-        self.model.load_state_dict(merged, strict=False)
+        load_merged(self.model, torch.load(pretrained_model, map_location='cpu', weights_only=False)['state_dict'], strict=False)
         self.model.to(self.device)
         self.model._modules.get(hook_name).register_forward_hook(hook_feature)
         if handover_sets is not None:          # the datasets are the sets the extraction has just written
@@ -381,9 +379,7 @@ class AT():
                 loader.dataset.release()
 
     def reload_LSTM(self, pretrained_lstm):
-        merged = self.lstm.state_dict()
-        merged.update(torch.load(pretrained_lstm, map_location='cpu', weights_only=False))
-        self.lstm.load_state_dict(merged)
+        load_merged(self.lstm, torch.load(pretrained_lstm, map_location='cpu', weights_only=False))
         print('loaded pretrained lstm from ' + pretrained_lstm)
 
     def _train_graphed(self, width, steps, feed, fetch=None, extra_check=None):

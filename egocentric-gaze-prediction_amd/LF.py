@@ -5,27 +5,16 @@ frame in device memory and gathers each batch there (data/late_resident.py); the
 import os
 
 import torch
-from torch.utils.data import DataLoader
 
 from . import dp
 from .data.lateDataset import lateDataset
-from .floss import BCELoss, floss
 from .models.late_fusion import late_fusion
 from .optim import FusedAdam
-from .utils import AverageMeter, aae_auc_from_rows, aae_auc_rows, computeAAEAUC, owned_state_dict, plot_loss
-from .SP import _progress
+from .trainloop import (EpochMeters, ReplayOrEager, make_criterion, progress as _progress, rank_loaders,
+                        split_by as _split)
+from .utils import aae_auc_from_rows, aae_auc_rows, computeAAEAUC, load_merged, owned_state_dict, plot_loss
 
 LF_GRAPH = os.environ.get("EGAZE_LF_GRAPH", "1") != "0"      # A/B knob: 0 = issue every LF training step launch by launch
-
-
-def _split(folder, val_name, task):
-    names = os.listdir(folder)
-    train = sorted(k for k in names if val_name not in k)
-    val = sorted(k for k in names if val_name in k)
-    if task is not None:
-        train = [k for k in train if task in k]
-        val = [k for k in val if task in k]
-    return train, val
 
 
 class GraphedLateIteration:
@@ -120,9 +109,7 @@ class LF():
         self.device = torch.device('cuda:' + device)
         self.save_name, self.save_path = save_name, save_path
         if pretrained_model is not None:
-            merged = self.model.state_dict()
-            merged.update(torch.load(pretrained_model, map_location='cpu', weights_only=False)['state_dict'])
-            self.model.load_state_dict(merged)
+            load_merged(self.model, torch.load(pretrained_model, map_location='cpu', weights_only=False)['state_dict'])
             print('loaded pretrained late fusion model from ' + pretrained_model)
         self.model.to(self.device)
         self.batch_size, self.num_epoch, self.epochnow, self.late_save_img = batch_size, num_epoch, 0, late_save_img
@@ -131,15 +118,9 @@ class LF():
         else:
             train_set, val_set = self._listed_sets(late_pred_path, late_feat_path, gt_path, val_name, task, resident, decode,
                                                    resident_gb)
-        collate = getattr(train_set, 'collate_fn', None)
-        # rank-sharded under torch.distributed (dp.RankShardSampler); the reference's loaders (LF.py:69-72) at world 1
-        self.train_sampler = dp.RankShardSampler(train_set, True, batch_size) if dp.world_size() > 1 else None
-        val_sampler = dp.RankShardSampler(val_set, False, batch_size, pad=False) if dp.world_size() > 1 else None
-        self.train_loader = DataLoader(dataset=train_set, batch_size=batch_size, shuffle=self.train_sampler is None,
-                                       sampler=self.train_sampler, num_workers=0, pin_memory=True, collate_fn=collate)
-        self.val_loader = DataLoader(dataset=val_set, batch_size=batch_size, shuffle=False, sampler=val_sampler,
-                                     num_workers=0, pin_memory=True, collate_fn=getattr(val_set, 'collate_fn', None))
-        self.criterion = (floss() if loss_function == 'f' else BCELoss()).to(self.device)
+        # (LF.py:69-72; no worker: lateDataset declares no loader_workers, the resident sets declare 0)
+        self.train_loader, self.val_loader, self.train_sampler = rank_loaders(train_set, val_set, batch_size, 0)
+        self.criterion = make_criterion(loss_function, self.device)
         self.optimizer = FusedAdam(self.model.parameters(), lr=lr)
         self.reducer = dp.attach(self.optimizer) if torch.distributed.is_initialized() else None
         from . import hipops
@@ -191,68 +172,46 @@ class LF():
 
     def _run(self, loader, train, every):
         from .data.STdatas import staged_batches
-        losses, auc, aae = AverageMeter(), AverageMeter(), AverageMeter()
+        meters = EpochMeters(timed=False)
+
+        def update(done):
+            for loss1, aae1, auc1 in done:
+                meters.update(loss1, 1, auc1, aae1)
         # the three maps of batch k + 1 cross PCIe on a copy stream while step k computes (LF.py:85-89 copies in the step)
         # The training step (forward + loss + zero_grad + backward + Adam, ~110 launches for ~1.4 ms of kernels) is captured
         # once and replayed (graphs.GraphedTrainStep); single process only -- the gradient reducer's hooks are host code.
-        graphed = None
+        # An exception / KeyboardInterrupt inside the loop must not leave the optimizer capturable with a stale host step count
+        # (ADVICE r3): leaving the block closes the step, which syncs the count back from the device
         use_graph = train and LF_GRAPH and dp.world_size() == 1 and self.device.type == 'cuda'
-        try:
-            return self._run_loop(loader, train, every, use_graph, losses, auc, aae)
-        finally:
-            # an exception / KeyboardInterrupt inside the loop must not leave the optimizer capturable with a stale host step
-            # count: close() syncs the count back from the device and leaves capturable mode
-            g = getattr(self, "_graphed", None)
-            if g is not None:
-                g.close()
-                self._graphed = None
-
-    def _run_loop(self, loader, train, every, use_graph, losses, auc, aae):
-        from .data.STdatas import staged_batches
-        graphed = None
-
-        def _update(done):
-            for loss1, aae1, auc1 in done:
-                auc.update(auc1)
-                aae.update(aae1)
-                losses.update(loss1)
-        for i, (sample, staged) in _progress(enumerate(staged_batches(loader, self.device, self.stage))):
-            maps = _maps(staged)                              # (feat, im, gt), or (fused, gt) of a resident batch
-            gt = maps[-1]
-            if use_graph and graphed is None:
-                graphed = self._graphed = GraphedLateIteration(self.model, self.criterion, self.optimizer, maps)
-            if graphed is not None and tuple(maps[0].shape) == graphed.shape:
-                graphed(*maps)                                # one replay = one LF.trainLate iteration (LF.py:90-100)
-                if graphed.full or (i + 1) % every == 0:
-                    _update(graphed.drain())
+        with ReplayOrEager(use_graph, lambda maps: GraphedLateIteration(self.model, self.criterion, self.optimizer,
+                                                                        maps)) as replay:
+            for i, (sample, staged) in _progress(enumerate(staged_batches(loader, self.device, self.stage))):
+                maps = _maps(staged)                              # (feat, im, gt), or (fused, gt) of a resident batch
+                graphed = replay.pick(tuple(maps[0].shape), maps)
+                if graphed is not None:
+                    graphed(*maps)                                # one replay = one LF.trainLate iteration (LF.py:90-100)
+                    if graphed.full or (i + 1) % every == 0:
+                        update(graphed.drain())
+                else:
+                    if replay.step is not None:
+                        update(replay.step.drain())               # (a trailing partial batch: the meters stay in iteration order)
+                    out = _forward(self.model, maps)
+                    loss = self.criterion(out, maps[-1])
+                    aae1, auc1, _ = computeAAEAUC(out.detach(), maps[-1])     # device kernel, maps stay in HBM (LF.py:92-94)
+                    meters.update(loss.item(), 1, auc1, aae1)
+                    if train:
+                        self.optimizer.zero_grad()
+                        loss.backward()
+                        self.optimizer.step()
                 if (i + 1) % every == 0:
                     print('Epoch: [{0}][{1}/{2}]\t''AUCAAE_late {auc.avg:.3f} ({aae.avg:.3f})\t'
-                          'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(self.epochnow, i + 1, len(loader) + 1, auc=auc,
-                                                                          loss=losses, aae=aae))
-                continue
-            if graphed is not None:
-                _update(graphed.drain())                      # (a trailing partial batch: the meters stay in iteration order)
-            out = _forward(self.model, maps)
-            loss = self.criterion(out, gt)
-            aae1, auc1, _ = computeAAEAUC(out.detach(), gt)          # device kernel, maps stay in HBM (LF.py:92-94)
-            auc.update(auc1)
-            aae.update(aae1)
-            losses.update(loss.item())
+                          'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(self.epochnow, i + 1, len(loader) + 1, auc=meters.auc,
+                                                                          loss=meters.loss, aae=meters.aae))
+            if replay.step is not None:
+                update(replay.step.drain())
             if train:
-                self.optimizer.zero_grad()
-                loss.backward()
-                self.optimizer.step()
-            if (i + 1) % every == 0:
-                print('Epoch: [{0}][{1}/{2}]\t''AUCAAE_late {auc.avg:.3f} ({aae.avg:.3f})\t'
-                      'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(self.epochnow, i + 1, len(loader) + 1, auc=auc,
-                                                                      loss=losses, aae=aae))
-        if graphed is not None:
-            _update(graphed.drain())
-        if train:
-            self.optimizer.check_finite()            # (NaN / inf gradient elements are skipped by the Adam kernel and reported here)
-        if dp.world_size() > 1:                      # global averages so that every rank agrees on the best epoch
-            return tuple(dp.reduce_meters((losses.sum, losses.count), (auc.sum, auc.count), (aae.sum, aae.count)))
-        return losses.avg, auc.avg, aae.avg
+                self.optimizer.check_finite()        # (NaN / inf gradient elements are skipped by the Adam kernel and reported here)
+        return meters.averages()                     # global, so that every rank agrees on the best epoch
 
     def trainLate(self):
         # like the reference, the model is never switched to eval(): BN uses batch statistics in both loops

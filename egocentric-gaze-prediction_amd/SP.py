@@ -5,28 +5,17 @@ HIP-backed mirrors (models.model_SP, floss, optim.FusedAdam).  ``device`` is the
 ('0' -> torch.device('cuda:0'), which is the HIP device on PyTorch-ROCm).
 """
 import os
-import time
 
 import torch
-from torch.utils.data import DataLoader
 
 from . import dp
-from .floss import BCELoss, floss
 from .models.model_SP import model_SP
 from .optim import FusedAdam
 from .data.STdatas import augmenting, staged_batches
-from .utils import (AverageMeter, cfg, change_key_names, computeAAEAUC, make_layers, owned_state_dict, plot_loss,
-                    save_checkpoint)
+from .trainloop import EpochMeters, make_criterion, progress as _progress, rank_loaders, validation_epoch
+from .utils import cfg, change_key_names, load_merged, make_layers, owned_state_dict, plot_loss, save_checkpoint
 
 VGG16_BN_URL = 'https://download.pytorch.org/models/vgg16_bn-6c64b313.pth'
-
-
-def _progress(it):
-    try:
-        from tqdm import tqdm
-        return tqdm(it)
-    except Exception:
-        return it
 
 
 def _load_vgg16_bn():
@@ -54,17 +43,7 @@ class SP():
         self.loss_function, self.num_epoch, self.batch_size = loss_function, num_epoch, batch_size
         self.device = torch.device('cuda:' + device)
         self.pretrained_spatial, self.pretrained_temporal = pretrained_spatial, pretrained_temporal
-        # one process per GPU: every rank draws a disjoint 1/world share of each epoch (dp.RankShardSampler); at world 1
-        # these are exactly the reference's loaders (SP.py:34-35)
-        self.train_sampler = dp.RankShardSampler(traindata, True, batch_size) if dp.world_size() > 1 else None
-        val_sampler = dp.RankShardSampler(valdata, False, batch_size, pad=False) if dp.world_size() > 1 else None
-        self.STTrainLoader = DataLoader(dataset=traindata, batch_size=batch_size, shuffle=self.train_sampler is None,
-                                        sampler=self.train_sampler, num_workers=getattr(traindata, 'loader_workers', 1),
-                                        pin_memory=True,
-                                        collate_fn=getattr(traindata, 'collate_fn', None))
-        self.STValLoader = DataLoader(dataset=valdata, batch_size=batch_size, shuffle=False, sampler=val_sampler,
-                                      num_workers=getattr(valdata, 'loader_workers', 1), pin_memory=True,
-                                      collate_fn=getattr(valdata, 'collate_fn', None))
+        self.STTrainLoader, self.STValLoader, self.train_sampler = rank_loaders(traindata, valdata, batch_size, 1)   # SP.py:34-35
         in_channels = 20
         self.model = model_SP(make_layers(cfg['D'], 3), make_layers(cfg['D'], in_channels))
         self.epochnow = 0
@@ -74,34 +53,26 @@ class SP():
             ckpt = torch.load(os.path.join(save_path, save_name), map_location='cpu', weights_only=False)
             self.epochnow = ckpt['epoch']
             pretrained_optimizer = ckpt['optimizer']
-            merged = self.model.state_dict()
-            merged.update(ckpt['state_dict'])
-            self.model.load_state_dict(merged)
+            load_merged(self.model, ckpt['state_dict'])
         elif resume == '0':          # ImageNet VGG16-BN into both encoders (SP.py:51-73)
             vgg = _load_vgg16_bn()
             flow = _strip_features(change_key_names(vgg, in_channels))
             rgb = _strip_features(vgg)
-            sd_s, sd_t = self.model.features_s.state_dict(), self.model.features_t.state_dict()
-            sd_s.update({k: v for k, v in rgb.items() if k in sd_s})
-            sd_t.update({k: v for k, v in flow.items() if k in sd_t})
-            self.model.features_s.load_state_dict(sd_s)
-            self.model.features_t.load_state_dict(sd_t)
+            load_merged(self.model.features_s, rgb, known_only=True)
+            load_merged(self.model.features_t, flow, known_only=True)
         else:                        # separately pre-trained streams, encoders frozen (SP.py:74-102)
             ps = torch.load(self.pretrained_spatial, map_location='cpu', weights_only=False)['state_dict']
             pt = torch.load(self.pretrained_temporal, map_location='cpu', weights_only=False)['state_dict']
             ps = {k: v for k, v in ps.items() if 'features' in k}
             pt = {k: v for k, v in pt.items() if 'features' in k}
-            sd_s, sd_t = self.model.features_s.state_dict(), self.model.features_t.state_dict()
             # the reference filters with the UN-stripped keys here (SP.py:91-92), so nothing matches and the
             # encoders keep their init before being frozen -- reproduced, not fixed
-            sd_s.update({k: v for k, v in ps.items() if k in sd_s})
-            sd_t.update({k: v for k, v in pt.items() if k in sd_t})
-            self.model.features_s.load_state_dict(sd_s)
-            self.model.features_t.load_state_dict(sd_t)
+            load_merged(self.model.features_s, ps, known_only=True)
+            load_merged(self.model.features_t, pt, known_only=True)
             for p in list(self.model.features_s.parameters()) + list(self.model.features_t.parameters()):
                 p.requires_grad = False
         self.model.to(self.device)
-        self.criterion = (floss() if loss_function == 'f' else BCELoss()).to(self.device)
+        self.criterion = make_criterion(loss_function, self.device)
         if resume != '0':            # only fusion + bn + decoder are trained (SP.py:109-111)
             params = (list(self.model.fusion.parameters()) + list(self.model.bn.parameters())
                       + list(self.model.decoder.parameters()))
@@ -117,8 +88,7 @@ class SP():
 
     def trainSP(self):
         self.model.train()
-        batch_time, losses = AverageMeter(), AverageMeter()
-        end = time.time()
+        meters = EpochMeters()
         self.optimizer.zero_grad()
         # batch k + 1 is copied (and normalised) on a copy stream while step k computes: data.STdatas.staged_batches
         with augmenting(getattr(self.STTrainLoader, 'dataset', None), self.augment, self.epochnow):
@@ -128,44 +98,20 @@ class SP():
                 loss.backward()
                 self.optimizer.step()
                 self.optimizer.zero_grad()
-                batch_time.update(time.time() - end)
-                losses.update(loss.item(), input_s.size(0))
-                end = time.time()
+                meters.update(loss.item(), input_s.size(0))
                 if (i + 1) % 1000 == 0:
                     print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
                           'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(self.epochnow, i + 1, len(self.STTrainLoader) + 1,
-                                                                          batch_time=batch_time, loss=losses))
+                                                                          batch_time=meters.batch_time, loss=meters.loss))
         self.optimizer.check_finite()        # raises if a step of the epoch met NaN / inf gradients (the kernel skipped those elements)
-        return losses.avg
+        return meters.loss.avg
 
     def testSP(self):
         dp.sync_buffers(self.model)                 # all ranks validate rank 0's BN running statistics
         self.model.eval()
-        batch_time, losses, auc, aae = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
-        end = time.time()
-        with torch.no_grad():
-            for i, (sample, (input_s, input_t, target)) in _progress(enumerate(staged_batches(self.STValLoader, self.device))):
-                output = self.model(input_s, input_t)
-                target = target.view(output.size())
-                loss = self.criterion(output, target)
-                losses.update(loss.item(), input_s.size(0))
-                batch_time.update(time.time() - end)
-                end = time.time()
-                aae1, auc1, _ = computeAAEAUC(output, target)          # device kernel (SP.py:170-174)
-                auc.update(auc1)
-                aae.update(aae1)
-                if (i + 1) % 1000 == 0:
-                    print('Test: [{0}/{1}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
-                          'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(i, len(self.STValLoader),
-                                                                          batch_time=batch_time, loss=losses))
-        if dp.world_size() > 1:                      # global averages: every rank takes the same 'best epoch' decision
-            loss_avg, auc_avg, aae_avg = dp.reduce_meters((losses.sum, losses.count), (auc.sum, auc.count),
-                                                          (aae.sum, aae.count))
-        else:
-            loss_avg, auc_avg, aae_avg = losses.avg, auc.avg, aae.avg
-        if dp.is_main():
-            print('AUC: {0}\t AAE: {1}'.format(auc_avg, aae_avg))
-        return loss_avg, auc_avg, aae_avg
+        batches = _progress(enumerate(staged_batches(self.STValLoader, self.device)))
+        return validation_epoch(batches, lambda staged: (self.model(staged[0], staged[1]), staged[2]), self.criterion,
+                                lambda i: (i + 1) % 1000 == 0, len(self.STValLoader))       # SP.py:150-186
 
     def train(self):
         train_loss, val_loss, best_loss = [], [], 100

@@ -17,9 +17,9 @@ import os
 
 import torch
 import torch.nn as nn
-from torch.utils.data import DataLoader
 
-from .utils import cfg, make_layers
+from .trainloop import extraction_loader
+from .utils import cfg, load_merged, make_layers
 
 
 def var_window(ind, size, H, W):
@@ -239,13 +239,10 @@ def extract_LSTM_training_data(save_path='../512w', trained_model='save/best_fus
         raise ValueError("extract_LSTM_training_data: into must be (train_set, val_set)")
     model = make_layers(cfg['D'], 3)
     sd = torch.load(trained_model, map_location='cpu', weights_only=False)['state_dict']
-    own = model.state_dict()
-    own.update({k[len('features_s.'):]: v for k, v in sd.items() if k.startswith('features_s.')})
-    model.load_state_dict(own)
+    load_merged(model, {k[len('features_s.'):]: v for k, v in sd.items() if k.startswith('features_s.')})
     model.to(torch.device('cuda:' + device)).eval()
     for k, (data, sub) in enumerate(((traindata, 'train'), (valdata, 'test'))):
-        loader = DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
-                            collate_fn=getattr(data, 'collate_fn', None))
+        loader = extraction_loader(data)
         if into is not None:
             extractw(loader, model, None, crop_size, device, align, shard=shard, into=into[k], chunk=chunk)
             continue

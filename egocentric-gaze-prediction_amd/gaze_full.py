@@ -6,7 +6,9 @@ import argparse
 import os
 
 import torch
-from torch.utils.data import DataLoader
+
+from .trainloop import extraction_loader, init_distributed, st_datasets
+from .trainloop import split_by as _split  # noqa: F401  (the tools and the tests list the folders with it)
 
 
 # The three in-memory hand-overs: (flag, [(flag it needs, why)], why it runs in one process, the flag it implies).  The parser
@@ -144,20 +146,20 @@ def build_parser():
     return p
 
 
-def _split(folder, val_name):
-    names = os.listdir(folder)
-    return sorted(k for k in names if val_name not in k), sorted(k for k in names if val_name in k)
+def _at_kwargs(args, STTrainData, STValData):
+    """AT's arguments from the command line, but for ``shard``, ``resident`` and the hand-over pair, which the two stages set."""
+    return dict(pretrained_model=args.pretrained_model, pretrained_lstm=args.pretrained_lstm,
+                extract_lstm=args.extract_lstm, crop_size=args.crop_size, num_epoch_lstm=args.num_epoch_lstm,
+                lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
+                device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
+                task=args.task, align=args.align, resident_gb=getattr(args, 'gpu_resident_gb', None))
 
 
 def _at_stage(args, STTrainData, STValData):
     from .AT import AT
-    att = AT(pretrained_model=args.pretrained_model, pretrained_lstm=args.pretrained_lstm,
-             extract_lstm=args.extract_lstm, crop_size=args.crop_size, num_epoch_lstm=args.num_epoch_lstm,
-             lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
-             device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
-             task=args.task, align=args.align, resident=getattr(args, 'lstm_resident', False) and args.train_lstm,
-             resident_gb=getattr(args, 'gpu_resident_gb', None), lstm_handover=getattr(args, 'lstm_handover', False),
-             lstm_handover_chunk=getattr(args, 'lstm_handover_chunk', 1))
+    att = AT(resident=getattr(args, 'lstm_resident', False) and args.train_lstm,
+             lstm_handover=getattr(args, 'lstm_handover', False), lstm_handover_chunk=getattr(args, 'lstm_handover_chunk', 1),
+             **_at_kwargs(args, STTrainData, STValData))
     if args.train_lstm:
         att.train()
     if args.extract_late and getattr(args, 'late_handover', False):
@@ -175,17 +177,13 @@ def _at_stage(args, STTrainData, STValData):
         if not args.train_lstm:
             att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data, into in ((STValData, late[1]), (STTrainData, late[0])):
-            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False, num_workers=0,
-                                        collate_fn=data.collate_fn), into=into)
+            att.extract_late(extraction_loader(data, workers=0), into=into)
         return tuple(late)
     if args.extract_late:
         if not args.train_lstm:
             att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data in (STValData, STTrainData):
-            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False,
-                                        num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
-                                        collate_fn=getattr(data, 'collate_fn', None)),
-                             args.extract_late_pred_folder, args.extract_late_feat_folder)
+            att.extract_late(extraction_loader(data), args.extract_late_pred_folder, args.extract_late_feat_folder)
 
 
 def _at_stage_sharded(args, STTrainData, STValData):
@@ -196,13 +194,8 @@ def _at_stage_sharded(args, STTrainData, STValData):
     from . import dp
     from .AT import AT
     shard = (dp.rank(), dp.world_size())
-    att = AT(pretrained_model=args.pretrained_model, pretrained_lstm=args.pretrained_lstm,
-             extract_lstm=args.extract_lstm, crop_size=args.crop_size, num_epoch_lstm=args.num_epoch_lstm,
-             lstm_save_img=args.lstm_save_img, save_path=args.save_path, save_name=args.save_lstm,
-             device=args.device, lstm_data_path=args.extract_lstm_path, traindata=STTrainData, valdata=STValData,
-             task=args.task, align=args.align, shard=shard,
-             resident=getattr(args, 'lstm_resident', False) and args.train_lstm and dp.is_main(),     # where AT.train runs
-             resident_gb=getattr(args, 'gpu_resident_gb', None))
+    att = AT(shard=shard, resident=getattr(args, 'lstm_resident', False) and args.train_lstm and dp.is_main(),   # where AT.train runs
+             **_at_kwargs(args, STTrainData, STValData))
     if args.train_lstm:
         if dp.is_main():
             try:
@@ -215,10 +208,7 @@ def _at_stage_sharded(args, STTrainData, STValData):
         # every rank runs the whole recurrence of extract_late: all of them take the weights from the one saved file
         att.reload_LSTM(os.path.join(args.save_path, args.save_lstm))
         for data in (STValData, STTrainData):
-            att.extract_late(DataLoader(dataset=data, batch_size=1, shuffle=False,
-                                        num_workers=getattr(data, 'loader_workers', 1), pin_memory=True,
-                                        collate_fn=getattr(data, 'collate_fn', None)),
-                             args.extract_late_pred_folder, args.extract_late_feat_folder, shard=shard)
+            att.extract_late(extraction_loader(data), args.extract_late_pred_folder, args.extract_late_feat_folder, shard=shard)
     dp.barrier()                          # LF lists the folders: not before every rank has written its files
 
 
@@ -247,40 +237,19 @@ def main(argv=None):
     from .AT import AT
     from .LF import LF
     from .SP import SP
-    from .data.STdatas import STDataset
     from .streamtrain import augment_spec
     from . import dp
-    if 'LOCAL_RANK' in os.environ and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        import datetime
-        args.device = os.environ['LOCAL_RANK']
-        torch.cuda.set_device(int(args.device))
-        # the LSTM training of the AT stage is sequential (rank 0 only) and takes hours: the other ranks wait for it on the HOST
-        # (_wait_for_rank0: a key in the process group's store, polled with sleep) -- not inside a device collective, which
-        # would spin for hours and need a multi-day collective timeout that also hides real hangs of the SP / LF all-reduces
-        torch.distributed.init_process_group(os.environ.get('EGAZE_DIST_BACKEND', 'nccl'),
-                                             timeout=datetime.timedelta(minutes=30))
+    import datetime
+    # the LSTM training of the AT stage is sequential (rank 0 only) and takes hours: the other ranks wait for it on the HOST
+    # (_wait_for_rank0: a key in the process group's store, polled with sleep) -- not inside a device collective, which
+    # would spin for hours and need a multi-day collective timeout that also hides real hangs of the SP / LF all-reduces
+    init_distributed(args, timeout=datetime.timedelta(minutes=30))
     flow_from = None
     if getattr(args, 'flow_handover', False):   # the flow paths are keys into the pool; --flowPath is never opened
         from .data.resident import FlowFrom
         flow_from = FlowFrom(args.framePath, bound=getattr(args, 'flow_bound', 20.0),
                              quality=getattr(args, 'flow_quality', 95))
-    listFolders = sorted(os.listdir(args.framePath if flow_from is not None else args.flowPath))
-    listGtFiles, listValGtFiles = _split(args.gtPath, args.val_name)
-    print('num of training samples: ', len(listGtFiles))
-    listfixsacTrain, listfixsacVal = _split(args.fixsacPath, args.val_name)
-    listTrainFiles, listValFiles = _split(args.imagePath, args.val_name)
-    print('num of val samples: ', len(listValFiles))
-    decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
-    resident = getattr(args, 'gpu_resident', False)
-    if resident:                            # the planes live on the device; batches are gathered there (data/resident.py)
-        from .data.resident import ResidentSTDataset as STDataset, fill_all
-    STTrainData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listTrainFiles, listGtFiles,
-                            listfixsacTrain, args.fixsacPath, raw_u8=True, decode=decode)   # bytes over PCIe, normalised on the GPU
-    STValData = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
-                          listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
-    if resident:
-        fill_all((STTrainData, STValData), torch.device('cuda:' + args.device), getattr(args, 'gpu_resident_gb', None),
-                 flow_from=flow_from)
+    STTrainData, STValData = st_datasets(args, flow_from=flow_from)
     os.makedirs(args.save_path, exist_ok=True)
     if args.train_sp:
         sp = SP(lr=args.lr, loss_save=args.sp_save_img, save_name=args.save_sp, save_path=args.save_path,

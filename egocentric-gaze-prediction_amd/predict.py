@@ -447,21 +447,15 @@ def load_models(trained_model, trained_late, trained_lstm, device):
     from .models.late_fusion import late_fusion
     from .models.LSTMnet import lstmnet
     from .models.model_SP import model_SP
-    from .utils import cfg, make_layers
+    from .utils import cfg, load_merged, make_layers
     model = model_SP(make_layers(cfg['D'], 3), make_layers(cfg['D'], 20))
-    merged = model.state_dict()
-    merged.update(torch.load(trained_model, map_location='cpu', weights_only=False)['state_dict'])
-    model.load_state_dict(merged, strict=False)
+    load_merged(model, torch.load(trained_model, map_location='cpu', weights_only=False)['state_dict'], strict=False)
     late = late_fusion()
-    merged = late.state_dict()
-    merged.update(torch.load(trained_late, map_location='cpu', weights_only=False)['state_dict'])
-    late.load_state_dict(merged)
+    load_merged(late, torch.load(trained_late, map_location='cpu', weights_only=False)['state_dict'])
     lstm = None
     if trained_lstm is not None:
         lstm = lstmnet()
-        merged = lstm.state_dict()
-        merged.update(torch.load(trained_lstm, map_location='cpu', weights_only=False))
-        lstm.load_state_dict(merged)
+        load_merged(lstm, torch.load(trained_lstm, map_location='cpu', weights_only=False))
         lstm.to(device)
     return model.to(device), lstm, late.to(device)
 

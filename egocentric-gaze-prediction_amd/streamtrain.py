@@ -17,15 +17,15 @@ Nothing runs at import: the reference parses argv, lists the data folders and do
 import argparse
 import functools
 import os
-import time
 
 import torch
 import torch.nn as nn
-from torch.utils.data import DataLoader
 
 from . import dp
-from .utils import (AverageMeter, FusedSequential, cfg, change_key_names, computeAAEAUC, init_like_reference, make_layers,
-                    owned_state_dict, plot_loss, save_checkpoint)
+from .trainloop import (EpochMeters, ReplayOrEager, init_distributed, make_criterion, progress as _progress, rank_loaders,
+                        st_datasets, validation_epoch)
+from .utils import (FusedSequential, cfg, change_key_names, init_like_reference, load_merged, make_layers, owned_state_dict,
+                    plot_loss, save_checkpoint)
 
 # run_spatialstream.py:17-53 / spatialstream.py:72-91 as (Cin, Cout) 3x3+ReLU blocks and 'U' = nearest x2 upsample; a 1x1 head
 # follows
@@ -39,14 +39,6 @@ STREAMS = {
     'temporal': dict(in_channels=20, key='flow', freeze=False, arch='flow', loss_save='loss_temporal.png',
                      save_name='best_temporal.pth.tar', val_print=lambda i: i % 1000 == 0),
 }
-
-
-def _progress(it):
-    try:
-        from tqdm import tqdm
-        return tqdm(it)
-    except Exception:
-        return it
 
 
 class StreamVGG(nn.Module):
@@ -154,46 +146,39 @@ def train_epoch(train_loader, model, criterion, optimizer, epoch, device, stream
     captured step, so seed and epoch passed by value never end up inside a graph."""
     spec = STREAMS[stream]
     device = torch.device(device)
-    batch_time, losses = AverageMeter(), AverageMeter()
+    meters = EpochMeters()
     model.train()
-    end = time.time()
     optimizer.zero_grad()
     encoder_grad = _optimised(model, optimizer)
     use_graph = hipgraph and dp.world_size() == 1 and device.type == 'cuda'
     stage = functools.partial(stage_stream, key=spec['key'], prepare=not use_graph)
     from .data.STdatas import augmenting, staged_batches
-    graphed = None
-    with augmenting(getattr(train_loader, 'dataset', None), augment, epoch):     # left on every way out
-        try:
-            for i, (sample, (inp, target)) in _progress(enumerate(staged_batches(train_loader, device, stage))):
-                if use_graph and graphed is None:
-                    graphed = GraphedStreamStep(model, criterion, optimizer, (inp, target), encoder_grad)
-                if graphed is not None and tuple(inp.shape) == graphed.shape:
-                    loss, output = graphed(inp, target)
-                else:
-                    if graphed is not None:
-                        optimizer.zero_grad()      # (a replay leaves its gradient in the buffers: the captured step zeroes first)
-                    output = step_forward(model, inp, encoder_grad)
-                    target = target.view(output.size())
-                    loss = criterion(output, target)
-                    loss.backward()
-                    optimizer.step()
-                    optimizer.zero_grad()
-                losses.update(loss.item(), inp.size(0))
-                batch_time.update(time.time() - end)
-                end = time.time()
-                if (i + 1) % every == 0:
-                    print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
-                          'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(epoch, i + 1, len(train_loader) + 1,
-                                                                          batch_time=batch_time, loss=losses))
-        finally:
-            if graphed is not None:        # leaves capturable mode, the host step count follows the device counter
-                graphed.close()
+    # both are left on every way out; leaving the replay closes the captured step: the optimizer leaves capturable mode, its
+    # host step count follows the device counter
+    with augmenting(getattr(train_loader, 'dataset', None), augment, epoch), \
+            ReplayOrEager(use_graph, lambda example: GraphedStreamStep(model, criterion, optimizer, example,
+                                                                       encoder_grad)) as replay:
+        for i, (sample, (inp, target)) in _progress(enumerate(staged_batches(train_loader, device, stage))):
+            graphed = replay.pick(tuple(inp.shape), (inp, target))
+            if graphed is not None:
+                loss, output = graphed(inp, target)
+            else:
+                if replay.step is not None:
+                    optimizer.zero_grad()      # (a replay leaves its gradient in the buffers: the captured step zeroes first)
+                output = step_forward(model, inp, encoder_grad)
+                target = target.view(output.size())
+                loss = criterion(output, target)
+                loss.backward()
+                optimizer.step()
+                optimizer.zero_grad()
+            meters.update(loss.item(), inp.size(0))
+            if (i + 1) % every == 0:
+                print('Epoch: [{0}][{1}/{2}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
+                      'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(epoch, i + 1, len(train_loader) + 1,
+                                                                      batch_time=meters.batch_time, loss=meters.loss))
     if hasattr(optimizer, 'check_finite'):
         optimizer.check_finite()        # raises if a step of the epoch met NaN / inf gradients (the kernel skipped those elements)
-    if dp.world_size() > 1:
-        return dp.reduce_meters((losses.sum, losses.count))[0]
-    return losses.avg
+    return meters.averages()[0]
 
 
 def validate(val_loader, model, criterion, epoch, device, stream='spatial'):
@@ -209,33 +194,11 @@ def evaluate(val_loader, model, criterion, epoch, device, stream='spatial'):
     spec = STREAMS[stream]
     device = torch.device(device)
     dp.sync_buffers(model)
-    batch_time, losses, aae, auc = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     model.eval()
-    end = time.time()
-    stage = functools.partial(stage_stream, key=spec['key'])
     from .data.STdatas import staged_batches
-    with torch.no_grad():
-        for i, (sample, (inp, target)) in _progress(enumerate(staged_batches(val_loader, device, stage))):
-            output = model(inp)
-            target = target.view(output.size())
-            loss = criterion(output, target)
-            losses.update(loss.item(), inp.size(0))
-            aae1, auc1, _ = computeAAEAUC(output.squeeze(), target.squeeze())
-            auc.update(auc1)
-            aae.update(aae1)
-            batch_time.update(time.time() - end)
-            end = time.time()
-            if spec['val_print'](i):
-                print('Test: [{0}/{1}]\t''Time {batch_time.val:.3f} ({batch_time.avg:.3f})\t'
-                      'Loss {loss.val:.4f} ({loss.avg:.4f})\t'.format(i, len(val_loader), batch_time=batch_time,
-                                                                      loss=losses))
-    if dp.world_size() > 1:
-        loss_avg, auc_avg, aae_avg = dp.reduce_meters((losses.sum, losses.count), (auc.sum, auc.count), (aae.sum, aae.count))
-    else:
-        loss_avg, auc_avg, aae_avg = losses.avg, auc.avg, aae.avg
-    if dp.is_main():
-        print('AUC: {0}\t AAE: {1}'.format(auc_avg, aae_avg))
-    return loss_avg, auc_avg, aae_avg
+    batches = _progress(enumerate(staged_batches(val_loader, device, functools.partial(stage_stream, key=spec['key']))))
+    return validation_epoch(batches, lambda staged: (model(staged[0]), staged[1]), criterion, spec['val_print'],
+                            len(val_loader), squeeze=True)
 
 
 def build_parser(stream):
@@ -316,54 +279,22 @@ def build_model(stream, resume=0, pretrained_model=None):
     from .SP import _load_vgg16_bn
     spec = STREAMS[stream]
     model = StreamVGG(make_layers(cfg['D'], spec['in_channels']), freeze_features=spec['freeze'])
-    model_dict = model.state_dict()
     if resume == 1:
         print('building model and loading from pretrained model...')
-        pretrained_dict = torch.load(pretrained_model, map_location='cpu', weights_only=False)['state_dict']
-        model_dict.update(pretrained_dict)
+        load_merged(model, torch.load(pretrained_model, map_location='cpu', weights_only=False)['state_dict'])
     else:
         print('building model and loading pretrained_dict from vgg...')
         pretrained_dict = _load_vgg16_bn()
         if spec['in_channels'] != 3:
             pretrained_dict = change_key_names(pretrained_dict, spec['in_channels'])
-        model_dict.update({k: v for k, v in pretrained_dict.items() if k in model_dict})
-    model.load_state_dict(model_dict)
+        load_merged(model, pretrained_dict, known_only=True)
     return model
 
 
 def make_loaders(args, key=None):
     """The reference's file lists and loaders (spatialstream.py:34-63); shuffled / sharded per rank under torch.distributed."""
-    from .data.STdatas import STDataset
-    listFolders = sorted(os.listdir(args.flowPath))
-    listGtFiles = sorted(k for k in os.listdir(args.gtPath) if args.val_name not in k)
-    listValGtFiles = sorted(k for k in os.listdir(args.gtPath) if args.val_name in k)
-    print('num of training samples: ', len(listGtFiles))
-    listfixsacTrain = sorted(k for k in os.listdir(args.fixsacPath) if args.val_name not in k)
-    listfixsacVal = sorted(k for k in os.listdir(args.fixsacPath) if args.val_name in k)
-    listTrainFiles = sorted(k for k in os.listdir(args.imagePath) if args.val_name not in k)
-    listValFiles = sorted(k for k in os.listdir(args.imagePath) if args.val_name in k)
-    print('num of val samples: ', len(listValFiles))
-    decode = 'gpu' if getattr(args, 'gpu_decode', False) else 'host'
-    resident = getattr(args, 'gpu_resident', False)
-    if resident:                            # the planes live on the device; batches are gathered there (data/resident.py)
-        from .data.resident import ResidentSTDataset as STDataset, fill_all
-    train_data = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listTrainFiles, listGtFiles,
-                           listfixsacTrain, args.fixsacPath, raw_u8=True, decode=decode)   # bytes over PCIe, normalised on the GPU
-    val_data = STDataset(args.flowPath, args.imagePath, args.gtPath, listFolders, listValFiles, listValGtFiles,
-                         listfixsacVal, args.fixsacPath, raw_u8=True, decode=decode)
-    if key is not None:                    # decode='gpu': only the stream's input and the ground truth are read and decoded
-        train_data.gpu_fields = val_data.gpu_fields = (key, 'gt')
-    if resident:
-        fill_all((train_data, val_data), torch.device('cuda:' + str(args.device)), getattr(args, 'gpu_resident_gb', None))
-    train_sampler = dp.RankShardSampler(train_data, True, args.batch_size) if dp.world_size() > 1 else None
-    val_sampler = dp.RankShardSampler(val_data, False, args.batch_size, pad=False) if dp.world_size() > 1 else None
-    train_loader = DataLoader(dataset=train_data, batch_size=args.batch_size, shuffle=train_sampler is None,
-                              sampler=train_sampler, num_workers=getattr(train_data, 'loader_workers', 0), pin_memory=True,
-                              collate_fn=train_data.collate_fn)
-    val_loader = DataLoader(dataset=val_data, batch_size=args.batch_size, shuffle=False, sampler=val_sampler,
-                            num_workers=getattr(val_data, 'loader_workers', 0), pin_memory=True,
-                            collate_fn=val_data.collate_fn)
-    return train_loader, val_loader, train_sampler
+    train_data, val_data = st_datasets(args, key)
+    return rank_loaders(train_data, val_data, args.batch_size, 0)
 
 
 def checkpoint_state(stream, epoch, model, optimizer):
@@ -375,20 +306,17 @@ def checkpoint_state(stream, epoch, model, optimizer):
 def main(stream, argv=None):
     """spatialstream.py / temporalstream.py as a function.  One process per GPU under torch.distributed.run (LOCAL_RANK /
     WORLD_SIZE set): gradients all-reduced (dp.attach), rank 0 writes the plot and the checkpoints.  Returns the model."""
-    from .floss import BCELoss, floss
     from .optim import FusedAdam
     spec = STREAMS[stream]
     args = build_parser(stream).parse_args(argv)
-    if 'LOCAL_RANK' in os.environ and int(os.environ.get('WORLD_SIZE', '1')) > 1 and not torch.distributed.is_initialized():
-        args.device = os.environ['LOCAL_RANK']
-        torch.cuda.set_device(int(args.device))
-        torch.distributed.init_process_group(os.environ.get('EGAZE_DIST_BACKEND', 'nccl'))
+    if not torch.distributed.is_initialized():
+        init_distributed(args)
     device = torch.device('cuda:' + args.device)
     train_loader, val_loader, train_sampler = make_loaders(args, spec['key'])
     model = build_model(stream, args.resume, args.pretrained_model)
     model.to(device)
     print('done!')
-    criterion = (floss() if args.loss_function == 'f' else BCELoss()).to(device)
+    criterion = make_criterion(args.loss_function, device)
     optimizer = FusedAdam(model.decoder.parameters(), lr=args.lr)           # spatialstream.py:216
     if torch.distributed.is_initialized():
         dp.attach(optimizer)

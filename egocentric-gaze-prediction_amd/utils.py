@@ -173,6 +173,14 @@ def owned_state_dict(module):
     return collections.OrderedDict((k, v.detach().clone()) for k, v in module.state_dict().items())
 
 
+def load_merged(module, state, strict=True, known_only=False):
+    """The reference's ``model_dict.update(state); load_state_dict(model_dict)``: the entries ``state`` lacks keep their
+    values.  ``known_only``: the entries of ``state`` that ``module`` does not have are dropped first."""
+    merged = module.state_dict()
+    merged.update({k: v for k, v in state.items() if k in merged} if known_only else state)
+    module.load_state_dict(merged, strict=strict)
+
+
 def save_checkpoint(state, filename, save_path):
     torch.save(state, os.path.join(save_path, filename))
 

@@ -31,7 +31,7 @@ from .data.STdatas import FLOW_MEAN, FLOW_STD, IMAGE_MEAN, IMAGE_STD, STDataset,
 from .data._io import imwrite_bgr
 from .models.LSTMnet import lstmnet
 from .models.model_SP import model_SP
-from .utils import cfg, make_layers, repackage_hidden
+from .utils import cfg, load_merged, make_layers, repackage_hidden
 
 hook_name = 'features_s'
 
@@ -198,9 +198,7 @@ def _load_into(module, path):
     sd = torch.load(path, map_location='cpu', weights_only=False)
     if isinstance(sd, dict) and 'state_dict' in sd:
         sd = sd['state_dict']
-    own = module.state_dict()
-    own.update(sd)
-    module.load_state_dict(own)
+    load_merged(module, sd)
 
 
 def main(argv=None):

@@ -227,6 +227,41 @@ def test_graphed_step_bit_identical_and_follows_encoder_loads(stream):
     assert int(sg[0]["features.1.num_batches_tracked"]) == 2      # reset to 0 by the load before step 7, then 7 and 8
 
 
+def test_train_epoch_interrupted_with_the_step_open():
+    """train_epoch(hipgraph=True) over four batches of 2 at 32 x 32 whose third batch raises (GraphedStreamStep is built at the
+    first batch and puts the optimizer into capturable mode; its first two calls are its eager warm-up steps): the step is
+    closed on the way out -- the optimizer has left capturable mode and its host step count is the number of completed steps,
+    the device counter's -- and an eager epoch on the same objects runs.  (test_hip_lf.py holds LF._run to the same.)"""
+    import math
+    from egaze_amd import streamtrain
+    from egaze_amd.floss import floss
+    from egaze_amd.optim import FusedAdam
+    x_s, _, gt, _ = synth.synth_sp_batch(8, 32, seed=13)
+    batches = [{"image": x_s[2 * i:2 * i + 2], "gt": gt[2 * i:2 * i + 2]} for i in range(4)]
+    model, _ = build("spatial")
+    opt = FusedAdam(model.decoder.parameters(), lr=1e-4)
+    crit = floss().to(DEV)
+
+    class Broken:
+        def __len__(self):
+            return len(batches)
+
+        def __iter__(self):
+            yield batches[0]
+            yield batches[1]
+            raise RuntimeError("third batch")
+    with pytest.raises(RuntimeError, match="third batch"):
+        streamtrain.train_epoch(Broken(), model, crit, opt, 0, DEV, "spatial", hipgraph=True)
+    torch.cuda.synchronize()
+    # (the loader runs one batch ahead of the step: the error arrives while step 1 or 2 is the last one issued)
+    assert not opt.capturable and opt.step_count in (1, 2)
+    assert int(opt.step_dev[0].item()) == opt.step_count
+    done = opt.step_count
+    loss = streamtrain.train_epoch(batches, model, crit, opt, 1, DEV, "spatial", hipgraph=False)
+    assert math.isfinite(loss) and loss > 0
+    assert not opt.capturable and opt.step_count == done + 4
+
+
 def _write_dataset(root, size=32):
     """The reference's on-disk layout (data/STdatas.py): flow/<video>/flow_{x,y}_NNNNN.jpg, images, gt maps named
     <video>_000000_NNNNN.png, fixation files; 3 training frames (batches of 2 + 1) and 2 validation frames ('Alireza')."""

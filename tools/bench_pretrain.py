@@ -6,7 +6,13 @@ frames/s at the same batch for context.  One JSON line per (stream, batch); time
 
 Algorithmic FLOP (2 per MAC): encoder forward + decoder forward + decoder data gradient (none for decoder.0, whose input is
 the encoder's output and needs no gradient) + decoder weight gradient; the 1x1 head, BatchNorm, pooling and loss are not
-counted.  The SP step is counted the same way by bench.py; here only its time is reported."""
+counted.  The SP step is counted the same way by bench.py; here only its time is reported.
+
+``train_epoch_hipgraph_ms_per_iter``: the loop itself, streamtrain.train_epoch(hipgraph=True) over an in-memory loader of
+--epoch_iters batches already on the device: the median interval between two of its requests for a batch (the first five, which
+hold the warm-up steps and the capture, left out), per epoch in ``train_epoch_rounds_ms`` and the median of those.  Against
+``hipgraph_ms_per_step`` it shows what the loop adds to a replay: staging, the meters and the loss read-back.  --loop_only
+prints that figure alone."""
 import argparse
 import json
 import os
@@ -95,6 +101,41 @@ def stream_step_ms(stream, B, size, steps, warmup, graphed):
     return ms, flops
 
 
+class _TimedLoader:
+    """One batch, handed out ``n`` times; notes when each is asked for."""
+
+    def __init__(self, sample, n):
+        self.sample, self.n, self.asked = sample, n, []
+
+    def __len__(self):
+        return self.n
+
+    def __iter__(self):
+        for _ in range(self.n):
+            self.asked.append(time.perf_counter())
+            yield self.sample
+
+
+def train_epoch_ms(stream, B, size, iters, rounds=3, skip=5):
+    """Per epoch, the median interval in ms between two batch requests of train_epoch(hipgraph=True)."""
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    spec = streamtrain.STREAMS[stream]
+    model = streamtrain.StreamVGG(make_layers(cfg['D'], spec['in_channels']), spec['freeze']).to(dev)
+    opt = FusedAdam(model.decoder.parameters(), lr=1e-7)
+    crit = floss().to(dev)
+    b = synthetic.sp_batch(B, size, dev, seed=1)
+    medians = []
+    for epoch in range(rounds):
+        loader = _TimedLoader({spec['key']: b[spec['key']], "gt": b["gt"]}, iters)
+        streamtrain.train_epoch(loader, model, crit, opt, epoch, dev, stream, hipgraph=True, every=10 ** 9)
+        gaps = sorted(1e3 * (t1 - t0) for t0, t1 in zip(loader.asked[skip:], loader.asked[skip + 1:]))
+        medians.append(gaps[len(gaps) // 2])
+    del model, opt, b
+    torch.cuda.empty_cache()
+    return medians
+
+
 def sp_step_ms(B, size, steps, warmup):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -121,10 +162,19 @@ def main():
     p.add_argument("--steps", type=int, default=30)
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--streams", nargs="+", default=["spatial", "temporal"])
+    p.add_argument("--epoch_iters", type=int, default=40)
+    p.add_argument("--loop_only", action="store_true")
     a = p.parse_args()
     for B in a.batches:
-        sp_ms = sp_step_ms(B, a.size, a.steps, a.warmup)
+        if not a.loop_only:
+            sp_ms = sp_step_ms(B, a.size, a.steps, a.warmup)
         for stream in a.streams:
+            rounds = train_epoch_ms(stream, B, a.size, a.epoch_iters)
+            loop = {"train_epoch_hipgraph_ms_per_iter": round(sorted(rounds)[len(rounds) // 2], 3),
+                    "train_epoch_rounds_ms": [round(m, 3) for m in rounds]}
+            if a.loop_only:
+                print(json.dumps({"stream": stream, "batch": B, "size": a.size, "epoch_iters": a.epoch_iters, **loop}), flush=True)
+                continue
             del WINDOWS[:]
             eager, flops = stream_step_ms(stream, B, a.size, a.steps, a.warmup, False)
             graph, _ = stream_step_ms(stream, B, a.size, a.steps, a.warmup, True)
@@ -137,7 +187,7 @@ def main():
                     ("encoder_fwd", "decoder_fwd", "decoder_dgrad", "decoder_wgrad"), flops)},
                 "eager_tflops": round(tf / eager * 1e3, 1), "hipgraph_tflops": round(tf / graph * 1e3, 1),
                 "sp_step_ms": round(sp_ms, 3), "sp_frames_per_s": round(B * 1e3 / sp_ms, 1),
-                "windows_ms": {"eager": WINDOWS[0], "hipgraph": WINDOWS[1]}}), flush=True)
+                "windows_ms": {"eager": WINDOWS[0], "hipgraph": WINDOWS[1]}, **loop}), flush=True)
 
 
 if __name__ == "__main__":
