@@ -462,7 +462,8 @@ class FusionBlock(torch.autograd.Function):
                 dw = H.conv3x3_wgrad(x2, dy2, out=sw).view(weight.shape)
         dfs, dft = data_grad()
         _close_fork(f, sw, dw, x2, dy2)
-        return (dfs, dft, _finish(weight, sw, dw), _finish(bias, sbias, db),
+        # (one launch computes both halves: a stream that needs no gradient gets None, not the view autograd would drop)
+        return (dfs if ng[0] else None, dft if ng[1] else None, _finish(weight, sw, dw), _finish(bias, sbias, db),
                 _finish(gamma, sg, dgamma if ng[4] else None), _finish(beta, sb, dbeta if ng[5] else None),
                 None, None, None, None, None, None)
 
